@@ -16,12 +16,27 @@ each rank taking 128/N rows, so every N runs the same search (196 steps per epoc
 ``--scaling weak`` keeps 128 rows per GPU (global batch 128 N: a different search,
 labelled as such).
 
-The same JSON line also carries
+A plain run (``--gpus N --steps K --warmup W``) does only what that headline needs: set-up, the
+warm-up and timed steps, the validation-batch timing the projection uses, and the result line.
+``--dump-outputs DIR`` also writes what the timed path computes (``DIR/<name>.npy``): after the timed
+steps the search goes back to its seeded initial state and the same captured step runs once more on
+the first batch, and that step's outputs are written. The search trajectory itself is chaotic under
+the reordering of the kernels' fp32 atomic sums (two runs drift ~1e-3 apart within 25 steps), while
+one step from a fixed state repeats to rounding, so two builds run with the same arguments can be
+compared output for output.
+Everything below runs only with ``--full`` (its keys are null in a plain run).
+
+With ``--full`` the same JSON line also carries
+* ``measured_search_wall_s``: the whole search run in-process next to its projection (``--full-search``);
+* ``per_rank_bn_ms_per_step`` / ``per_rank_floor_ms`` (N > 1): the step with per-rank BatchNorm, and one
+  rank's step on its own at the per-rank batch;
+* ``b1_trials_per_hour`` / ``b5_experiment_wall_s``: the B1-shaped and the B5 experiment through the scheduler;
 * ``trials_per_hour``: BASELINE config 2 end to end through the scheduler (TPE over the
   MNIST MLP, ``--trial-slots`` trials per GPU at a time over all N GPUs, warm workers), run by rank 0
   in a child process *before* any rank touches the GPU (``bench_trials.py``);
 * ``torch_eager_ms_per_step``: the same search step on the PyTorch op backend launched
-  eagerly (MIOpen / hipBLASLt / PyTorch kernels, no HIP graph), a same-node comparator.
+  eagerly (MIOpen / hipBLASLt / PyTorch kernels, no HIP graph), a same-node comparator
+  (``torch_graph_ms_per_step`` and ``module_eager_ms_per_step`` likewise).
 
 Lower is better; vs_baseline = value / 282 s (B5, 1x NVIDIA GPU, end to end).
 Data: synthetic CIFAR-10-shaped tensors resident in HBM, random-init weights.
@@ -43,6 +58,7 @@ import sys
 import time
 
 B5_SECONDS = 282.0
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000  # --dump-outputs: all arrays together stay under 64 MB
 PRIMS = ["separable_convolution_3x3", "dilated_convolution_3x3", "dilated_convolution_5x5", "avg_pooling_3x3",
          "max_pooling_3x3", "skip_connection"]
 CONFIGS = {
@@ -59,6 +75,14 @@ def main():
     ap.add_argument("--config", default="b5", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=128, help="global batch (strong) / per-GPU batch (weak)")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything next to the headline: the scheduler experiments (--trials, --b1, "
+                         "--experiment), the same-GPU comparators, the whole in-process search, and at N > 1 the "
+                         "per-rank-BN step and the per-rank floor. Off: those options are ignored, their keys null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run the timed step once more from the seeded initial state on the "
+                         "first batch and write what it computed (loss, logits, weights, alphas, BN running "
+                         "statistics) to DIR/<name>.npy as float32 (rank 0)")
     ap.add_argument("--trials", type=int, default=12, help="trials per GPU of the trials/hour experiment (0: skip)")
     ap.add_argument("--trial-slots", type=int, default=1,
                     help="concurrent trials per GPU in the trials/hour experiment (warm workers per GPU)")
@@ -93,6 +117,10 @@ def main():
     args = ap.parse_args()
     if args.sync_bn < 0:
         args.sync_bn = 1 if args.scaling == "strong" else 0
+    if not args.full:
+        # a plain run measures the headline only
+        args.trials = args.b1 = args.experiment = args.comparator_steps = 0
+        args.full_search = args.floor = args.per_rank_bn = 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N`: become N ranks, one per GPU, before anything touches the GPU
@@ -169,6 +197,7 @@ def main():
         if dev.type == "cuda":
             torch.cuda.synchronize()
 
+    init_state = [t.clone() for t in search._state_tensors()] if args.dump_outputs else None
     for i in range(args.warmup):
         (tx, ty), (vx, vy) = batches[i % len(batches)]
         search.step(tx, ty, vx, vy)
@@ -185,6 +214,16 @@ def main():
     dt = time.perf_counter() - t0
     ms_step = comm.allreduce_max(dt * 1000.0 / args.steps)
     loss = float(search.loss_out)
+    if args.dump_outputs:
+        # the same step (same captured graph) once more from the seeded initial state, on every rank
+        with torch.no_grad():
+            for t, s0 in zip(search._state_tensors(), init_state):
+                t.copy_(s0)
+        (tx, ty), (vx, vy) = batches[0]
+        search.step(tx, ty, vx, vy)
+        sync()
+        if comm.rank == 0:
+            dump_outputs(args.dump_outputs, search)
 
     # validation pass cost (no_grad forward, BN in eval mode) -- part of every search epoch; the
     # validation batches go EVAL_GROUP at a time through one captured forward (the same losses and
@@ -317,6 +356,7 @@ def main():
             "ranks_seen": comm.world_size,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": round(ms_step, 4),
             "higher_is_better": False,
             "scaling": args.scaling,
@@ -372,6 +412,25 @@ def main():
         }
         print(json.dumps(out), flush=True)
     comm.destroy()
+
+
+def dump_outputs(path: str, search) -> None:
+    """What a caller of ``DartsSearch.step`` holds after the step just run: the loss it returned, the
+    logits behind it, and the search state it updated (weights, architecture alphas, BN running
+    statistics), one float32 ``<name>.npy`` each. An array over its share of DUMP_LIMIT_BYTES is cut
+    to a fixed (seed 0) sorted sample of its flattened elements."""
+    import numpy as np
+
+    out = {"loss": search.loss_out, "logits": search.logits_out, "weights": search.W, "alphas": search.A,
+           "bn_running_mean": search.bn.mean, "bn_running_var": search.bn.var}
+    out = {k: v for k, v in out.items() if v is not None}
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // (4 * len(out))  # elements per array
+    for name, t in out.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def self_launch(n: int) -> int:

@@ -21,7 +21,7 @@ if [ "$SEL" = all ] || [ "$SEL" = tests ]; then
   step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit 1
 fi
 if [ "$SEL" = all ] || [ "$SEL" = bench ]; then
-  step bench 600 python bench.py || exit 1
-  step bench-default 600 python bench.py --config default --steps 10 --warmup 3 --trials 0 --comparator-steps 3 --full-search 0 || exit 1
+  step bench 600 python bench.py --full || exit 1
+  step bench-default 600 python bench.py --config default --steps 10 --warmup 3 --trials 0 --comparator-steps 3 --full-search 0 --full || exit 1
 fi
 echo done >> $L

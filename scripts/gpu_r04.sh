@@ -29,7 +29,7 @@ for s in "$@"; do
     tests)
       step pytest-gpu 1200 python -u -m pytest tests -m gpu -x -v --timeout 240 --timeout-method thread -p no:cacheprovider || exit 1
       step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit 1 ;;
-    bench) step bench 600 python bench.py || exit 1 ;;
+    bench) step bench 600 python bench.py --full || exit 1 ;;
     quick) step quick 300 python bench.py --trials 0 --b1 0 --comparator-steps 0 --full-search 0 || exit 1 ;;
     default) step default 400 python bench.py --config default --steps 10 --warmup 3 --trials 0 --b1 0 --comparator-steps 0 --full-search 0 || exit 1 ;;
     tl)

@@ -19,6 +19,6 @@ step bench-dp2-perrank 400 python bench.py --gpus 2 --steps 20 --warmup 5 --tria
 for b in 64 32 16; do
   step bench-b$b 300 python bench.py --batch $b --steps 20 --warmup 5 --trials 0 --b1 0 --comparator-steps 0 --full-search 0 || exit 1
 done
-step bench-full 900 python bench.py || exit 1
+step bench-full 900 python bench.py --full || exit 1
 step pmc-bw 600 bash scripts/gpu_pmc_bw.sh || exit 1
 echo done >> $L

@@ -21,5 +21,5 @@ for r in 1 2; do
   step "b5 group1" 300 env KATIB_DARTS_EVAL_GROUP=1 python bench.py --steps 40 --warmup 5 $Q --full-search 0 || exit 1
   step "b5 group8" 300 env KATIB_DARTS_EVAL_GROUP=8 python bench.py --steps 40 --warmup 5 $Q --full-search 0 || exit 1
 done
-step "b5 full-search" 300 python bench.py --steps 40 --warmup 5 $Q --full-search 1 || exit 1
+step "b5 full-search" 300 python bench.py --steps 40 --warmup 5 $Q --full-search 1 --full || exit 1
 echo done >> $L

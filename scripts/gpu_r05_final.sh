@@ -13,7 +13,7 @@ timeout -k 10 1000 python -u -m pytest tests -q --timeout 300 --timeout-method t
 echo "=== smoke $(date +%T)" >> $L
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" >> $L 2>&1 || exit 1
 echo "=== bench N=1 $(date +%T)" >> $L
-timeout -k 10 600 python bench.py >> $L 2>&1 || exit 1
+timeout -k 10 600 python bench.py --full >> $L 2>&1 || exit 1
 echo "=== bench N=2 (shared GPU) $(date +%T)" >> $L
 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
   --master-port 29551 bench.py --gpus 2 --steps 10 --warmup 3 --trials 0 --b1 0 --experiment 0 \

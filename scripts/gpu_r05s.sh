@@ -14,5 +14,5 @@ timeout -k 10 1000 python -u -m pytest tests -x -q --timeout 300 --timeout-metho
 echo "=== smoke $(date +%T)" >> $L
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" >> $L 2>&1 || exit 1
 echo "=== bench $(date +%T)" >> $L
-timeout -k 10 600 python bench.py >> $L 2>&1 || exit 1
+timeout -k 10 600 python bench.py --full >> $L 2>&1 || exit 1
 echo done >> $L

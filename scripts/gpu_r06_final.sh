@@ -13,7 +13,7 @@ timeout -k 10 1000 python -u -m pytest tests -q --timeout 300 --timeout-method t
 echo "=== smoke $(date +%T)" >> $L
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" >> $L 2>&1 || exit 1
 echo "=== bench N=1 $(date +%T)" >> $L
-timeout -k 10 600 python bench.py >> $L 2>&1 || exit 1
+timeout -k 10 600 python bench.py --full >> $L 2>&1 || exit 1
 echo "=== bench --gpus 2 (both ranks on this one GPU: a rehearsal of the N>1 path, not a scaling number) $(date +%T)" >> $L
 timeout -k 10 600 python bench.py --gpus 2 --steps 20 --warmup 5 --trials 0 --b1 0 --experiment 0 --comparator-steps 0 \
   --full-search 0 --floor 0 >> $L 2>&1 || exit 1

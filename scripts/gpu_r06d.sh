@@ -13,7 +13,7 @@ timeout -k 10 1000 python -u -m pytest tests -q --timeout 300 --timeout-method t
 echo "=== smoke $(date +%T)" >> $L
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" >> $L 2>&1 || exit 1
 echo "=== bench N=1 $(date +%T)" >> $L
-timeout -k 10 600 python bench.py >> $L 2>&1 || exit 1
+timeout -k 10 600 python bench.py --full >> $L 2>&1 || exit 1
 echo "=== gpt2 member $(date +%T)" >> $L
 timeout -k 10 300 python -m katib_amd.workloads.gpt2_pbt --batch-size 16 --steps 40 --checkpoint-dir /tmp/g2 --save-files 0 >> $L 2>&1 || exit 1
 echo "=== gpt2 prof $(date +%T)" >> $L

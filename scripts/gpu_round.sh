@@ -21,5 +21,5 @@ step mnist-mlp 300 python -m katib_amd.workloads.mnist_mlp --epochs 3 || exit 1
 step resnet18 600 python -m katib_amd.workloads.resnet_cifar --epochs 1 --max-steps 60 || exit 1
 step gpt2-small 600 python -m katib_amd.workloads.gpt2_pbt --steps 30 --batch-size 16 || exit 1
 step bench-trials 900 python bench_trials.py --trials 24 --parallel 8 --epochs 3 || exit 1
-step bench-darts 600 python bench.py || exit 1
+step bench-darts 600 python bench.py --full || exit 1
 echo done >> $L

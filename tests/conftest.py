@@ -7,7 +7,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-REFERENCE = "/root/reference"
+# settings files of the reference project (example Experiments, swagger.json, katib-config.yaml), stored as data
+REFERENCE = os.path.join(ROOT, "tests", "golden", "reference")
 
 
 def pytest_configure(config):

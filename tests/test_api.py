@@ -14,7 +14,7 @@ from katib_amd.api.validation import ValidationError, validate_experiment
 from katib_amd.api.yaml_io import load_documents, load_experiment
 from katib_amd.controller.manifest import ConfigMapStore, Generator
 
-REF = "/root/reference/examples/v1beta1"
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference", "examples", "v1beta1")
 EXAMPLES = sorted(glob.glob(REF + "/hp-tuning/*.yaml") + glob.glob(REF + "/early-stopping/*.yaml")
                   + glob.glob(REF + "/nas/*.yaml") + glob.glob(REF + "/metrics-collector/*.yaml")
                   + glob.glob(REF + "/resume-experiment/*.yaml"))
@@ -25,7 +25,6 @@ def test_positional_feasible_space():
     assert fs.list == ["a", "b"] and fs.min is None
 
 
-@pytest.mark.skipif(not EXAMPLES, reason="reference examples not mounted")
 @pytest.mark.parametrize("path", EXAMPLES, ids=lambda p: os.path.relpath(p, REF))
 def test_reference_examples_roundtrip_default_validate(path):
     with open(path) as f:

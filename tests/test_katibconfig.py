@@ -262,11 +262,10 @@ def test_scheduler_config_applies_reference_defaults():
 
 
 def test_reference_install_config_loads():
-    path = "/root/reference/manifests/v1beta1/installs/katib-standalone/katib-config.yaml"
     import os
 
-    if not os.path.exists(path):
-        pytest.skip("reference manifests not mounted")
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference", "manifests", "v1beta1",
+                        "installs", "katib-standalone", "katib-config.yaml")
     docs = [d for d in yaml.safe_load_all(open(path)) if d]
     text = docs[0]["data"][KC.KATIB_CONFIG_TAG] if docs[0].get("kind") == "ConfigMap" else yaml.safe_dump(docs[0])
     st = ConfigMapStore()

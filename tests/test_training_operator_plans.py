@@ -16,8 +16,8 @@ from katib_amd.api.yaml_io import load_experiment
 from katib_amd.controller import jobs
 from katib_amd.controller.jobs import assign_ports, make_plan
 
-REF = "/root/reference/examples/v1beta1/kubeflow-training-operator"
-need_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference examples not present")
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference", "examples", "v1beta1",
+                   "kubeflow-training-operator")
 
 
 def _plan(name, container):
@@ -37,7 +37,6 @@ def _ports(plan):
     return out
 
 
-@need_ref
 def test_tfjob_plan_tf_config():
     plan = _plan("tfjob-mnist-with-summaries.yaml", "tensorflow")
     assert plan.kind == "TFJob" and plan.ports_managed and len(plan.replicas) == 2
@@ -51,7 +50,6 @@ def test_tfjob_plan_tf_config():
         assert p in jobs._RECENT_PORTS
 
 
-@need_ref
 def test_mxjob_plan_dmlc_env():
     plan = _plan("mxjob-byteps.yaml", "mxnet")
     roles = [(r.role, r.env["DMLC_ROLE"]) for r in plan.replicas]
@@ -61,14 +59,12 @@ def test_mxjob_plan_dmlc_env():
     assert plan.primary.role == "scheduler"
 
 
-@need_ref
 def test_mpijob_plan_launcher_only():
     plan = _plan("mpijob-horovod.yaml", "training-container")
     assert [r.role for r in plan.replicas] == ["launcher"] and plan.replicas[0].primary
     assert "mpirun" in " ".join(plan.replicas[0].argv)
 
 
-@need_ref
 def test_xgboostjob_plan_ranks():
     plan = _plan("xgboostjob-lightgbm.yaml", "xgboost")
     ranks = [r.env["RANK"] for r in plan.replicas]
@@ -76,7 +72,6 @@ def test_xgboostjob_plan_ranks():
     assert len({r.env["MASTER_PORT"] for r in plan.replicas}) == 1 and plan.replicas[0].role == "master"
 
 
-@need_ref
 @pytest.mark.parametrize("name,container", [("tfjob-mnist-with-summaries.yaml", "tensorflow"),
                                             ("mxjob-byteps.yaml", "mxnet"),
                                             ("xgboostjob-lightgbm.yaml", "xgboost"),
