@@ -26,6 +26,30 @@ hipError_t ln_bwd(const bf16* dy, const float* xin, const float* mean, const flo
 hipError_t ln_reduce_params(const float* part_g, const float* part_b, int nblk, int D, bf16* dgamma, bf16* dbeta,
                             hipStream_t st, const float* part_r = nullptr, bf16* dbias = nullptr);
 
+// Dropout fused into the residual LayerNorm kernels (transformer_drop.hip). The keep mask is never
+// stored: element e = row * D + col of a site's [M, D] tensor takes word e & 3 of
+// Philox4x32-10(counter = (q lo, q hi, site, step), key = (seed lo, seed hi)), q = e >> 2, is kept
+// iff word >= thr = round(p * 2^32) and is then multiplied by scale = 1 / (1 - p). step is a device
+// scalar (the fp32 optimizer step counter, read as uint32) so a captured graph replays fresh masks.
+struct DropSpec {
+  const float* step;
+  uint64_t seed;
+  uint32_t site;
+  uint32_t thr;
+  float scale;
+};
+// ln_fwd with r required: xo = x32 + (keep ? scale * r : 0), LN of xo.
+hipError_t ln_fwd_drop(const float* x32, const bf16* r, float* xo, const bf16* gamma, const bf16* beta, bf16* y,
+                       float* mean, float* rstd, int M, int D, float eps, const DropSpec& dp, hipStream_t st);
+// ln_bwd with dr required: dx as ln_bwd, dr = keep ? bf16(scale * dx) : 0, part_r sums that dr.
+hipError_t ln_bwd_drop(const bf16* dy, const float* xin, const float* mean, const float* rstd, const bf16* gamma,
+                       const float* dres, float* dx, bf16* dr, float* part_g, float* part_b, int M, int D,
+                       const DropSpec& dp, hipStream_t st, float* part_r = nullptr);
+// x = keep ? scale * x : 0 in place over n fp32 elements (n % 4 == 0) of a row-major [M, D] tensor.
+hipError_t dropout_f32(float* x, int64_t n, const DropSpec& dp, hipStream_t st);
+// the keep mask itself, one byte (0 / 1) per element (n % 4 == 0); for tests.
+hipError_t dropout_mask(uint8_t* out, int64_t n, const DropSpec& dp, hipStream_t st);
+
 // tanh-approximate GELU on bf16 (n % 8 == 0).
 hipError_t gelu_fwd(const bf16* u, bf16* g, int64_t n, hipStream_t st);
 hipError_t gelu_bwd(const bf16* u, const bf16* dy, bf16* du, int64_t n, hipStream_t st);

@@ -4,6 +4,8 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
+#include <cmath>
+
 #include "gemm_bf16.h"
 #include "transformer.h"
 
@@ -86,6 +88,91 @@ void ln_bwd(const Tensor& dy, const Tensor& xin, const Tensor& mean, const Tenso
                 dx.data_ptr<float>(), drp, part_g.data_ptr<float>(), part_b.data_ptr<float>(), (int)M, (int)D,
                 stream(), prp),
      "ln_bwd");
+}
+
+// dropout site description shared by the four dropout entry points (transformer.h DropSpec)
+T_::DropSpec drop_spec(double p, int64_t site, int64_t seed, const Tensor& step) {
+  TORCH_CHECK(p >= 0.0 && p <= 0.9, "dropout: p must be in [0, 0.9], got ", p);
+  TORCH_CHECK(site >= 0 && site < (1ll << 32), "dropout: site must fit 32 bits");
+  TORCH_CHECK(seed >= 0, "dropout: seed must be non-negative");
+  TORCH_CHECK(step.is_cuda() && step.scalar_type() == at::kFloat && step.numel() == 1,
+              "dropout: step must be an fp32[1] GPU tensor");
+  T_::DropSpec dp;
+  dp.step = step.data_ptr<float>();
+  dp.seed = (uint64_t)seed;
+  dp.site = (uint32_t)site;
+  dp.thr = (uint32_t)std::floor(p * 4294967296.0 + 0.5);
+  dp.scale = 1.0f / (1.0f - (float)p);
+  return dp;
+}
+
+void ln_fwd_drop(const Tensor& x32, const Tensor& r, const Tensor& xo, const Tensor& gamma, const Tensor& beta,
+                 const Tensor& y, const Tensor& mean, const Tensor& rstd, double eps, double p, int64_t site,
+                 int64_t seed, const Tensor& step) {
+  TORCH_CHECK(x32.dim() == 2, "x32 must be [M, D]");
+  const int64_t M = x32.size(0), D = x32.size(1);
+  TORCH_CHECK(D % 256 == 0 && D / 256 >= 1 && D / 256 <= 8 && D / 256 != 7, "ln_fwd_drop: D must be 256*{1..6,8}");
+  chk(x32, at::kFloat, M * D, "x32");
+  chk(gamma, at::kBFloat16, D, "gamma");
+  chk(beta, at::kBFloat16, D, "beta");
+  chk(y, at::kBFloat16, M * D, "y");
+  chk(mean, at::kFloat, M, "mean");
+  chk(rstd, at::kFloat, M, "rstd");
+  chk(r, at::kBFloat16, M * D, "r");
+  chk(xo, at::kFloat, M * D, "xo");
+  const T_::DropSpec dp = drop_spec(p, site, seed, step);
+  ok(T_::ln_fwd_drop(x32.data_ptr<float>(), bp(r), xo.data_ptr<float>(), bp(gamma), bp(beta), bp(y),
+                     mean.data_ptr<float>(), rstd.data_ptr<float>(), (int)M, (int)D, (float)eps, dp, stream()),
+     "ln_fwd_drop");
+}
+
+void ln_bwd_drop(const Tensor& dy, const Tensor& xin, const Tensor& mean, const Tensor& rstd, const Tensor& gamma,
+                 const c10::optional<Tensor>& dres, const Tensor& dx, const Tensor& dr, const Tensor& part_g,
+                 const Tensor& part_b, const c10::optional<Tensor>& part_r, double p, int64_t site, int64_t seed,
+                 const Tensor& step) {
+  TORCH_CHECK(xin.dim() == 2, "xin must be [M, D]");
+  const int64_t M = xin.size(0), D = xin.size(1);
+  TORCH_CHECK(D % 256 == 0 && D / 256 >= 1 && D / 256 <= 8 && D / 256 != 7, "ln_bwd_drop: D must be 256*{1..6,8}");
+  chk(dy, at::kBFloat16, M * D, "dy");
+  chk(xin, at::kFloat, M * D, "xin");
+  chk(mean, at::kFloat, M, "mean");
+  chk(rstd, at::kFloat, M, "rstd");
+  chk(gamma, at::kBFloat16, D, "gamma");
+  chk(dx, at::kFloat, M * D, "dx");
+  chk(dr, at::kBFloat16, M * D, "dr");
+  const int64_t nb = T_::ln_bwd_blocks((int)M);
+  chk(part_g, at::kFloat, nb * D, "part_g");
+  chk(part_b, at::kFloat, nb * D, "part_b");
+  const float* dresp = nullptr;
+  if (dres.has_value()) {
+    chk(*dres, at::kFloat, M * D, "dres");
+    dresp = dres->data_ptr<float>();
+  }
+  float* prp = nullptr;
+  if (part_r.has_value()) {
+    chk(*part_r, at::kFloat, nb * D, "part_r");
+    prp = part_r->data_ptr<float>();
+  }
+  const T_::DropSpec dp = drop_spec(p, site, seed, step);
+  ok(T_::ln_bwd_drop(bp(dy), xin.data_ptr<float>(), mean.data_ptr<float>(), rstd.data_ptr<float>(), bp(gamma), dresp,
+                     dx.data_ptr<float>(), bp(dr), part_g.data_ptr<float>(), part_b.data_ptr<float>(), (int)M, (int)D,
+                     dp, stream(), prp),
+     "ln_bwd_drop");
+}
+
+void dropout_f32(const Tensor& x, double p, int64_t site, int64_t seed, const Tensor& step) {
+  TORCH_CHECK(x.dim() == 2 && x.size(1) % 4 == 0 && x.numel() > 0, "dropout_f32: x must be [M, D], D % 4 == 0");
+  chk(x, at::kFloat, x.numel(), "x");
+  ok(T_::dropout_f32(x.data_ptr<float>(), x.numel(), drop_spec(p, site, seed, step), stream()), "dropout_f32");
+}
+
+void dropout_mask(const Tensor& out, double p, int64_t site, int64_t seed, const Tensor& step) {
+  TORCH_CHECK(out.dim() == 2 && out.size(1) % 4 == 0 && out.numel() > 0,
+              "dropout_mask: out must be [M, D], D % 4 == 0");
+  chk(out, at::kBool, out.numel(), "out");
+  ok(T_::dropout_mask(reinterpret_cast<uint8_t*>(out.data_ptr()), out.numel(), drop_spec(p, site, seed, step),
+                      stream()),
+     "dropout_mask");
 }
 
 void ln_reduce(const Tensor& part_g, const Tensor& part_b, const Tensor& dgamma, const Tensor& dbeta,
@@ -382,6 +469,17 @@ void register_transformer(py::module& m) {
         py::arg("dy"), py::arg("xin"), py::arg("mean"), py::arg("rstd"), py::arg("gamma"), py::arg("dres"),
         py::arg("dx"), py::arg("dr"), py::arg("part_g"), py::arg("part_b"), py::arg("part_r") = py::none());
   m.def("ln_bwd_blocks", &ln_bwd_blocks);
+  m.def("ln_fwd_drop", &ln_fwd_drop, "ln_fwd with Philox dropout of r: xo = x32 + (keep ? scale * r : 0)",
+        py::arg("x32"), py::arg("r"), py::arg("xo"), py::arg("gamma"), py::arg("beta"), py::arg("y"), py::arg("mean"),
+        py::arg("rstd"), py::arg("eps"), py::arg("p"), py::arg("site"), py::arg("seed"), py::arg("step"));
+  m.def("ln_bwd_drop", &ln_bwd_drop, "ln_bwd with the same mask on dr (and on its column sums part_r)",
+        py::arg("dy"), py::arg("xin"), py::arg("mean"), py::arg("rstd"), py::arg("gamma"), py::arg("dres"),
+        py::arg("dx"), py::arg("dr"), py::arg("part_g"), py::arg("part_b"), py::arg("part_r"), py::arg("p"),
+        py::arg("site"), py::arg("seed"), py::arg("step"));
+  m.def("dropout_f32", &dropout_f32, "Philox dropout in place over an fp32 [M, D] tensor", py::arg("x"), py::arg("p"),
+        py::arg("site"), py::arg("seed"), py::arg("step"));
+  m.def("dropout_mask", &dropout_mask, "the keep mask of a dropout site as bool [M, D] (tests)", py::arg("out"),
+        py::arg("p"), py::arg("site"), py::arg("seed"), py::arg("step"));
   m.def("ln_reduce", &ln_reduce, "sum LayerNorm parameter-gradient partials into bf16 grads (+ a bias gradient)",
         py::arg("part_g"), py::arg("part_b"), py::arg("dgamma"), py::arg("dbeta"), py::arg("part_r") = py::none(),
         py::arg("dbias") = py::none());

@@ -38,6 +38,7 @@ import torch.nn.functional as F
 # attn-proj / fc2 bias gradients summed by the LayerNorm backward that writes their output gradient
 _LN_BIAS = True  # (module attribute; False: a separate column-sum pass per bias, as before)
 
+from ..ops.transformer import Drop, check_dropout_p
 from ..utils.tracing import gpu_range
 
 
@@ -67,6 +68,9 @@ class GPT2Flat:
         self.device = torch.device(device)
         self.ops = ops
         self.dtype = dtype
+        # residual / embedding dropout, training only; the mask stream is keyed by (site, seed, step_t)
+        self.dropout = check_dropout_p(getattr(cfg, "dropout", 0.0))
+        self.seed = int(seed)
         self.V = cfg.vocab
         self.Vp = (cfg.vocab + 63) // 64 * 64
         d = cfg.d
@@ -154,30 +158,42 @@ class GPT2Flat:
         x = F.embedding(idx.reshape(-1), self.w["wte.weight"]).float()
         return (x.view(B, T, -1) + self.w["wpe.weight"][:T].float()).view(B * T, -1)
 
-    def forward(self, idx, save: bool = False):
-        """Logits [B*T, Vp] (pad columns are zero-weight rows; ignore them)."""
+    def _drop(self, site: int, train: bool = True):
+        """The dropout site ``site`` of a training pass (None: no dropout). Site ids: 2 i = block i's
+        proj output, 2 i + 1 = its fc2 output, 2 n_layer = the embedding sum. ``step_t`` (completed
+        optimizer steps) advances after the backward, so the forward and the backward of one step draw
+        the same mask, and a resumed checkpoint continues the stream."""
+        return Drop(self.dropout, site, self.seed, self.step_t) if (train and self.dropout > 0.0) else None
+
+    def forward(self, idx, save: bool = False, train: bool = False):
+        """Logits [B*T, Vp] (pad columns are zero-weight rows; ignore them). ``train``: apply
+        ``cfg.dropout`` to the embedding sum and to every proj / fc2 output (inside the residual-add
+        LayerNorm that consumes it). Attention-probability dropout is not implemented."""
         c, ops = self.cfg, self.ops
         B, T = idx.shape
         H = c.n_head
-        resid = self._embed(idx)
+        resid = ops.dropout_(self._embed(idx), self._drop(2 * c.n_layer, train))  # no-op without dropout
         pending = None
         acts = []
         for i in range(c.n_layer):
             pre = "blocks.%d." % i
-            sa, h1, mu1, rs1 = ops.ln_fwd(resid, pending, self.w[pre + "ln1.weight"], self.w[pre + "ln1.bias"])
+            sa, h1, mu1, rs1 = ops.ln_fwd(resid, pending, self.w[pre + "ln1.weight"], self.w[pre + "ln1.bias"],
+                                          drop=self._drop(2 * i - 1, train and i > 0))  # the lower block's fc2
             qkv = self._lin(h1, pre + "qkv")
             o, lse = ops.attn_fwd(qkv, B, T, H, c.d // H)
             a = self._lin(o, pre + "proj")
-            sb, h2, mu2, rs2 = ops.ln_fwd(sa, a, self.w[pre + "ln2.weight"], self.w[pre + "ln2.bias"])
+            sb, h2, mu2, rs2 = ops.ln_fwd(sa, a, self.w[pre + "ln2.weight"], self.w[pre + "ln2.bias"],
+                                          drop=self._drop(2 * i, train))
             u, gl = ops.linear_gelu(h2, self.w[pre + "fc.weight"], self.w[pre + "fc.bias"])  # GELU in the epilogue
             pending = self._lin(gl, pre + "fc2")
             resid = sb
             if save:
                 acts.append((sa, h1, mu1, rs1, qkv, o, lse, sb, h2, mu2, rs2, u, gl))
-        sf, hf, muf, rsf = ops.ln_fwd(resid, pending, self.w["ln_f.weight"], self.w["ln_f.bias"])
+        sf, hf, muf, rsf = ops.ln_fwd(resid, pending, self.w["ln_f.weight"], self.w["ln_f.bias"],
+                                      drop=self._drop(2 * c.n_layer - 1, train))
         logits = ops.linear(hf, self.w["wte.weight"], None)  # tied LM head
         if save:
-            self._saved = (acts, sf, hf, muf, rsf)
+            self._saved = (acts, sf, hf, muf, rsf, train)
         return logits
 
     # ---------------------------------------------------------------- training step
@@ -188,7 +204,7 @@ class GPT2Flat:
         M, H, d = B * T, c.n_head, c.d
         tgt = tgt.reshape(-1)
         with gpu_range("gpt2.forward"):
-            logits = self.forward(idx, save=True)
+            logits = self.forward(idx, save=True, train=True)
         return self._backward(idx, tgt, logits)
 
     def _backward(self, idx, tgt, logits):
@@ -200,7 +216,7 @@ class GPT2Flat:
 
     def _backward_body(self, idx, tgt, logits, B, T, M, H, d):
         c, ops = self.cfg, self.ops
-        acts, sf, hf, muf, rsf = self._saved
+        acts, sf, hf, muf, rsf, train = self._saved
         self._saved = None
         # forward + backward of the cross-entropy in one pass over the logits (the gradient overwrites them)
         loss_rows, lse_ce, dlog = ops.xent_train(logits, tgt, self.gscale, self.V)
@@ -217,9 +233,11 @@ class GPT2Flat:
         dr = torch.empty((M, d), device=self.device, dtype=self.dtype)
         # each LayerNorm backward also column-sums the dr it writes: the bias gradient of the linear layer
         # whose output gradient dr is (the top block's fc2 here, proj after ln2, the lower block's fc2 after ln1)
+        # with dropout, the same kernel masks dr (and so the bias gradient) with the mask the forward drew
         lb = _LN_BIAS
         ops.ln_bwd(dh, sf, muf, rsf, self.w["ln_f.weight"], G, dr, g["ln_f.weight"], g["ln_f.bias"],
-                   accumulate=False, dbias=g["blocks.%d.fc2.bias" % (c.n_layer - 1)] if lb else None)
+                   accumulate=False, dbias=g["blocks.%d.fc2.bias" % (c.n_layer - 1)] if lb else None,
+                   drop=self._drop(2 * c.n_layer - 1, train))
         for i in reversed(range(c.n_layer)):
             pre = "blocks.%d." % i
             sa, h1, mu1, rs1, qkv, o, lse, sb, h2, mu2, rs2, u, gl = acts.pop()
@@ -233,7 +251,7 @@ class GPT2Flat:
             dh2 = ops.dgrad(du, self.w[pre + "fc.weight"])
             del du
             ops.ln_bwd(dh2, sb, mu2, rs2, self.w[pre + "ln2.weight"], G, dr, g[pre + "ln2.weight"],
-                       g[pre + "ln2.bias"], dbias=g[pre + "proj.bias"] if lb else None)
+                       g[pre + "ln2.bias"], dbias=g[pre + "proj.bias"] if lb else None, drop=self._drop(2 * i, train))
             # attention: dr is now the gradient of proj's output
             ops.wgrad(dr, o, g[pre + "proj.weight"])
             if not lb:
@@ -245,9 +263,10 @@ class GPT2Flat:
             del dqkv
             ops.ln_bwd(dh1, sa, mu1, rs1, self.w[pre + "ln1.weight"], G, dr if i > 0 else None,
                        g[pre + "ln1.weight"], g[pre + "ln1.bias"],
-                       dbias=g["blocks.%d.fc2.bias" % (i - 1)] if (i > 0 and lb) else None)
-        # embeddings: G is the gradient of wte[idx] + wpe[:T]
-        Gb = G.to(self.dtype)
+                       dbias=g["blocks.%d.fc2.bias" % (i - 1)] if (i > 0 and lb) else None,
+                       drop=self._drop(2 * i - 1, train and i > 0))
+        # embeddings: G is the gradient of the (dropped) sum wte[idx] + wpe[:T]
+        Gb = ops.dropout_(G, self._drop(2 * c.n_layer, train)).to(self.dtype)
         g["wte.weight"].index_add_(0, idx.reshape(-1), Gb)
         gw = g["wpe.weight"]
         torch.sum(Gb.view(B, T, d), 0, out=gw[:T])

@@ -16,6 +16,10 @@ Contracts (``M`` rows, ``D`` features, ``Vp`` padded vocabulary of which ``V`` a
     ``G += LN'(dy)`` in place (``G`` fp32 residual-stream gradient; ``G`` is *set* when
     ``accumulate=False``), ``dr[:] = G`` cast to the activation dtype when ``dr`` is given,
     ``dgamma/dbeta`` written.
+``ln_fwd(..., drop=Drop(p, site, seed, step))`` / ``ln_bwd(..., drop=...)`` / ``dropout_(x, drop)``
+    dropout of the residual branch ``r`` (forward) and of its gradient ``dr`` (backward), and in place
+    over an fp32 tensor; the mask comes from Philox4x32-10 (contract above :func:`philox4x32`), the
+    same in both backends bit for bit. ``drop=None`` or ``p == 0``: the calls above, unchanged.
 ``attn_fwd(qkv, B, T, H) -> (o, lse)``
     causal softmax attention with head dim 64; ``qkv`` is ``[B*T, 3*H*64]`` (q | k | v, heads
     contiguous), ``o`` is ``[B*T, H*64]``, ``lse`` ``[B, H, T]`` = log2-sum-exp2 of the
@@ -29,6 +33,7 @@ from __future__ import annotations
 import importlib
 import math
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -55,22 +60,127 @@ def _kern():
 #   profiles/gpt2_gelu_dgrad_bias_ab_r05.log).
 
 
+# ---------------------------------------------------------------- dropout (Philox4x32-10)
+# The dropout mask of the GPT-2 trial is never stored: the kernels of csrc/hip/transformer_drop.hip and
+# the torch oracle below recompute it, forward and backward, from the same counter-based generator.
+# For a site applied to a row-major [M, D] tensor, element e = row * D + col:
+#   q = e >> 2 (64-bit); counter = (q & 0xffffffff, q >> 32, site, step); key = (seed & 0xffffffff, seed >> 32);
+#   the element takes output word e & 3 and is kept iff word >= thr = round(p * 2^32);
+#   kept values are multiplied by scale = 1 / (1 - p), computed in fp32.
+# step = the model's device step counter (completed optimizer steps) as uint32.
+PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
+PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+DROPOUT_MAX_P = 0.9
+_M32 = 0xFFFFFFFF
+
+
+class Drop(NamedTuple):
+    """One dropout site: probability, site id, the trial's seed, the device step counter."""
+    p: float
+    site: int
+    seed: int
+    step: "torch.Tensor | int"
+
+
+def check_dropout_p(p: float) -> float:
+    p = float(p)
+    if not 0.0 <= p <= DROPOUT_MAX_P:  # also rejects NaN
+        raise ValueError("dropout must be in [0, %g], got %r" % (DROPOUT_MAX_P, p))
+    return p
+
+
+def dropout_threshold(p: float) -> int:
+    return int(math.floor(check_dropout_p(p) * 4294967296.0 + 0.5))
+
+
+def dropout_scale(p: float) -> float:
+    one = torch.ones((), dtype=torch.float32)
+    return float(one / (one - torch.tensor(check_dropout_p(p), dtype=torch.float32)))
+
+
+def _mulhilo32(a: int, b):
+    """(hi, lo) words of the 64-bit product of the constant ``a`` and the uint32 values ``b`` (int64
+    tensor). A 32 x 32 product overflows int64, so it is assembled from 16-bit limbs."""
+    ah, al = a >> 16, a & 0xFFFF
+    bh, bl = b >> 16, b & 0xFFFF
+    p0 = al * bl
+    mid = al * bh + ah * bl + (p0 >> 16)  # < 3 * 2^32
+    return ah * bh + (mid >> 16), ((mid & 0xFFFF) << 16) | (p0 & 0xFFFF)
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10 on uint32 words carried in int64 tensors: ``counter`` = 4 and ``key`` = 2 words
+    (Python ints or broadcastable tensors); returns the 4 output words as int64 tensors."""
+    def word(v):
+        v = v.to(torch.int64) if torch.is_tensor(v) else torch.tensor(int(v), dtype=torch.int64)
+        return v & _M32
+
+    c0, c1, c2, c3 = (word(v) for v in counter)
+    k0, k1 = (word(v) for v in key)
+    for _ in range(10):
+        hi0, lo0 = _mulhilo32(PHILOX_M0, c0)
+        hi1, lo1 = _mulhilo32(PHILOX_M1, c2)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + PHILOX_W0) & _M32, (k1 + PHILOX_W1) & _M32
+    return c0, c1, c2, c3
+
+
+def dropout_mask(M: int, D: int, p: float, site: int, seed: int, step, device=None):
+    """Keep mask (bool [M, D]) of one dropout site at one step; ``step`` is an int or the device
+    step tensor (read as uint32, no host sync)."""
+    if D % 4:
+        raise ValueError("dropout_mask: D must be a multiple of 4")
+    if torch.is_tensor(step):
+        device = step.device if device is None else device
+        step = step.reshape(()).to(device=device, dtype=torch.int64)
+    q = torch.arange(M * D // 4, dtype=torch.int64, device=device)  # q = e >> 2 for e = row * D + col
+    words = philox4x32((q & _M32, q >> 32, int(site), step), (int(seed) & _M32, (int(seed) >> 32) & _M32))
+    return (torch.stack(words, -1) >= dropout_threshold(p)).view(M, D)  # word e & 3 = the last axis
+
+
+def _active(drop) -> bool:
+    return drop is not None and check_dropout_p(drop.p) > 0.0
+
+
 class TorchOps:
     name = "torch"
 
     def __init__(self, eps: float = 1e-5):
         self.eps = eps
 
+    # ---------------------------------------------------------------- dropout
+    def dropout_mask(self, M, D, drop, device=None):
+        return dropout_mask(M, D, drop.p, drop.site, drop.seed, drop.step, device)
+
+    def _dropped(self, t, drop):
+        """``keep ? scale * t : 0`` in fp32 for t [M, D]."""
+        keep = self.dropout_mask(t.shape[0], t.shape[1], drop, t.device)
+        t = t.float()
+        return torch.where(keep, t * dropout_scale(drop.p), torch.zeros_like(t))
+
+    def dropout_(self, x, drop):
+        """``x = keep ? scale * x : 0`` in place (fp32 [M, D])."""
+        if _active(drop):
+            x.copy_(self._dropped(x, drop))
+        return x
+
     # ---------------------------------------------------------------- LayerNorm
-    def ln_fwd(self, x32, r, gamma, beta):
-        xin = x32 if r is None else x32 + r.float()
+    def ln_fwd(self, x32, r, gamma, beta, drop=None):
+        if _active(drop):
+            if r is None:
+                raise ValueError("ln_fwd: dropout applies to the residual branch r")
+            xin = x32 + self._dropped(r, drop)
+        else:
+            xin = x32 if r is None else x32 + r.float()
         mean = xin.mean(-1)
         var = ((xin - mean[:, None]) ** 2).mean(-1)
         rstd = torch.rsqrt(var + self.eps)
         y = ((xin - mean[:, None]) * rstd[:, None] * gamma.float() + beta.float()).to(gamma.dtype)
         return xin, y, mean, rstd
 
-    def ln_bwd(self, dy, xin, mean, rstd, gamma, G, dr, dgamma, dbeta, accumulate=True, dbias=None):
+    def ln_bwd(self, dy, xin, mean, rstd, gamma, G, dr, dgamma, dbeta, accumulate=True, dbias=None, drop=None):
+        """``drop``: the dropout site of the branch whose output gradient ``dr`` is - ``dr`` (and so
+        ``dbias``) takes the masked, scaled gradient; ``G`` is unchanged by it."""
         D = xin.shape[-1]
         g = dy.float()
         xh = (xin - mean[:, None]) * rstd[:, None]
@@ -80,7 +190,11 @@ class TorchOps:
             G.add_(dx)
         else:
             G.copy_(dx)
-        if dr is not None:
+        if _active(drop):
+            if dr is None:
+                raise ValueError("ln_bwd: dropout applies to the branch gradient dr")
+            dr.copy_(self._dropped(G, drop))
+        elif dr is not None:
             dr.copy_(G)
         dgamma.copy_((g * xh).sum(0))
         dbeta.copy_(g.sum(0))
@@ -234,24 +348,53 @@ class HipOps:
         self.k.gemm_nt(x, w, b, u, g)
         return u, g
 
-    def ln_fwd(self, x32, r, gamma, beta):
+    # dropout (csrc/hip/transformer_drop.hip): the mask is recomputed by every kernel from Philox4x32-10
+    # keyed by (site, seed, device step counter) - see the contract at the top of this module
+    def dropout_mask(self, M, D, drop, device=None):
+        step = drop.step
+        if not torch.is_tensor(step):
+            step = torch.full((1,), float(step), device=device, dtype=torch.float32)
+        out = torch.empty((M, D), device=step.device, dtype=torch.bool)
+        self.k.dropout_mask(out, check_dropout_p(drop.p), drop.site, drop.seed, step)
+        return out
+
+    def dropout_(self, x, drop):
+        """``x = keep ? scale * x : 0`` in place (fp32 [M, D], D % 4 == 0)."""
+        if _active(drop):
+            self.k.dropout_f32(x, drop.p, drop.site, drop.seed, drop.step)
+        return x
+
+    def ln_fwd(self, x32, r, gamma, beta, drop=None):
         M, D = x32.shape
         xin = x32 if r is None else torch.empty_like(x32)
         y = torch.empty((M, D), device=x32.device, dtype=torch.bfloat16)
         mean = torch.empty(M, device=x32.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
+        if _active(drop):
+            if r is None:
+                raise ValueError("ln_fwd: dropout applies to the residual branch r")
+            self.k.ln_fwd_drop(x32, r, xin, gamma, beta, y, mean, rstd, self.eps, drop.p, drop.site, drop.seed,
+                               drop.step)
+            return xin, y, mean, rstd
         self.k.ln_fwd(x32, r, None if r is None else xin, gamma, beta, y, mean, rstd, self.eps)
         return xin, y, mean, rstd
 
-    def ln_bwd(self, dy, xin, mean, rstd, gamma, G, dr, dgamma, dbeta, accumulate=True, dbias=None):
+    def ln_bwd(self, dy, xin, mean, rstd, gamma, G, dr, dgamma, dbeta, accumulate=True, dbias=None, drop=None):
         """``dbias``: also the bias gradient of the linear layer whose output gradient ``dr`` is
-        (column sums of dr, accumulated by the same kernel instead of a colsum pass)."""
+        (column sums of dr, accumulated by the same kernel instead of a colsum pass). ``drop``: the
+        dropout site of that layer's output - ``dr`` and ``dbias`` take the masked, scaled gradient."""
         M, D = xin.shape
         nb = self.k.ln_bwd_blocks(M)
         want = dbias is not None and dr is not None
         part = torch.empty((3 if want else 2, nb, D), device=xin.device, dtype=torch.float32)
-        self.k.ln_bwd(dy, xin, mean, rstd, gamma, G if accumulate else None, G, dr, part[0], part[1],
-                      part[2] if want else None)
+        if _active(drop):
+            if dr is None:
+                raise ValueError("ln_bwd: dropout applies to the branch gradient dr")
+            self.k.ln_bwd_drop(dy, xin, mean, rstd, gamma, G if accumulate else None, G, dr, part[0], part[1],
+                               part[2] if want else None, drop.p, drop.site, drop.seed, drop.step)
+        else:
+            self.k.ln_bwd(dy, xin, mean, rstd, gamma, G if accumulate else None, G, dr, part[0], part[1],
+                          part[2] if want else None)
         self.k.ln_reduce(part[0], part[1], dgamma, dbeta, part[2] if want else None, dbias if want else None)
 
     def gelu_fwd(self, u):

@@ -16,6 +16,13 @@ graph. ``--impl module`` is the plain ``nn.Module`` + autocast + ``torch.optim.A
 path (the CPU default and the numerical oracle). Data: synthetic Markov-chain tokens
 resident in HBM.
 
+``--dropout p`` (0 <= p <= 0.9, a PBT-tunable hyperparameter, ``examples/pbt/pbt-gpt2-small-dropout.yaml``)
+drops the embedding sum and every attention-proj / MLP-fc2 output while training; evaluation never
+drops and attention-probability dropout is fixed at 0. The flat model's masks come from a
+counter-based generator keyed by ``--seed`` and the checkpointed step counter (fused into the
+LayerNorm kernels, ``csrc/hip/transformer_drop.hip``), so a child that resumes a parent continues
+its mask stream; the ``nn.Module`` path uses ``F.dropout`` (statistically, not bitwise, the same).
+
 Checkpoints: the parent's state is fetched GPU-to-GPU from the warm worker that
 trained it (:mod:`katib_amd.parallel.p2p_ckpt`, peer copy over xGMI); ``model.pt`` +
 ``optim.pt`` (``torch.save``, loaded with ``weights_only=True``) in
@@ -28,6 +35,7 @@ Validation-accuracy=<token accuracy>`` at the end.
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import math
 import os
 import time
@@ -38,7 +46,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..models.gpt2 import GPT2Flat
-from ..ops.transformer import get_ops
+from ..ops.transformer import DROPOUT_MAX_P, get_ops
 from ..parallel import p2p_ckpt
 from .common import CapturedStep, Timer, device, markov_tokens, report
 
@@ -78,6 +86,10 @@ class Block(nn.Module):
         self.fc = nn.Linear(c.d, 4 * c.d)
         self.fc2 = nn.Linear(4 * c.d, c.d)
         self.h = c.n_head
+        self.p = c.dropout  # residual dropout on the proj / fc2 outputs (a float: state_dict keys unchanged)
+
+    def _drop(self, t):
+        return F.dropout(t, self.p, self.training) if self.p > 0 else t
 
     def forward(self, x):
         B, T, D = x.shape
@@ -86,8 +98,8 @@ class Block(nn.Module):
         k = k.view(B, T, self.h, D // self.h).transpose(1, 2)
         v = v.view(B, T, self.h, D // self.h).transpose(1, 2)
         a = F.scaled_dot_product_attention(q, k, v, is_causal=True)
-        x = x + self.proj(a.transpose(1, 2).reshape(B, T, D))
-        return x + self.fc2(F.gelu(self.fc(self.ln2(x)), approximate="tanh"))
+        x = x + self._drop(self.proj(a.transpose(1, 2).reshape(B, T, D)))
+        return x + self._drop(self.fc2(F.gelu(self.fc(self.ln2(x)), approximate="tanh")))
 
 
 class GPT(nn.Module):
@@ -114,6 +126,8 @@ class GPT(nn.Module):
     def forward(self, idx):
         B, T = idx.shape
         x = self.wte(idx) + self.wpe(torch.arange(T, device=idx.device))
+        if self.c.dropout > 0:  # framework RNG: the statistical reference of GPT2Flat's Philox masks
+            x = F.dropout(x, self.c.dropout, self.training)
         for b in self.blocks:
             x = b(x)
         return F.linear(self.ln_f(x), self.wte.weight)  # tied LM head
@@ -141,7 +155,13 @@ def parse_args(argv):
     p.add_argument("--impl", default="auto", choices=["auto", "flat", "module"],
                    help="flat: flat-buffer model on the HIP kernels (GPU default); module: nn.Module + autograd")
     p.add_argument("--ops", default="auto", choices=["auto", "hip", "torch"], help="kernel backend of --impl flat")
-    return p.parse_args(argv)
+    p.add_argument("--dropout", type=float, default=0.0,
+                   help="dropout on the embedding sum and the proj / fc2 outputs, 0 <= p <= %g "
+                        "(attention-probability dropout is fixed at 0)" % DROPOUT_MAX_P)
+    args = p.parse_args(argv)
+    if not 0.0 <= args.dropout <= DROPOUT_MAX_P:
+        p.error("--dropout must be in [0, %g], got %r" % (DROPOUT_MAX_P, args.dropout))
+    return args
 
 
 def _tensors(obj):
@@ -179,7 +199,7 @@ def main(argv=None):
     dev = device()
     cuda = dev.type == "cuda"
     torch.manual_seed(args.seed)
-    cfg = PRESETS[args.model]
+    cfg = dataclasses.replace(PRESETS[args.model], dropout=args.dropout)
     T = args.seq_len or cfg.ctx
     toks = markov_tokens(args.num_tokens, vocab=cfg.vocab, seed=99, dev=dev)
     n_train = int(len(toks) * 0.9)
