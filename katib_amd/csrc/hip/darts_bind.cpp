@@ -6,6 +6,7 @@
 #include <c10/hip/HIPStream.h>
 
 #include "darts_ops.h"
+#include "darts_plane_layout.h"
 
 using namespace katib_hip;
 using at::Tensor;
@@ -201,7 +202,9 @@ static bool fill_dwpw(const py::tuple& t, DwPwFwdArgs& a, int64_t K, int64_t dil
   const int Ho = z.size(2), Wo = z.size(3);
   TORCH_CHECK(dw.numel() == C * K * K && pw.numel() == C * C, "weight shapes");
   TORCH_CHECK(z.size(0) == N && z.size(1) == C && d.sizes() == z.sizes(), "output shapes");
-  TORCH_CHECK(64 % Wo == 0 && Ho % (64 / Wo) == 0, "tile constraint: 64 % Wo == 0 and Ho % (64/Wo) == 0");
+  // (C = 4 / 8 / 16 always run the row-band plane kernels, which take any width)
+  TORCH_CHECK(C == 4 || C == 8 || C == 16 || (64 % Wo == 0 && Ho % (64 / Wo) == 0),
+              "tile constraint: 64 % Wo == 0 and Ho % (64/Wo) == 0");
   TORCH_CHECK(C <= kMaxC, "C too large");
   TORCH_CHECK(Ho == (H + 2 * pad - dil * (K - 1) - 1) / S + 1, "output height mismatch");
   a.x = x.data_ptr(); a.dw = dw.data_ptr<float>(); a.pw = pw.data_ptr<float>();
@@ -217,7 +220,7 @@ static bool fill_dwpw(const py::tuple& t, DwPwFwdArgs& a, int64_t K, int64_t dil
     int nb = std::max(1, std::min(Ho / 4, 2048 / std::max(N * nentries, 1)));
     auto band_bytes = [&](int b) {
       const int BR = (Ho + b - 1) / b;
-      return (size_t)C * ((BR - 1) * S + (K - 1) * dil + 1) * (W + 2 * pad) * sizeof(float);
+      return (size_t)C * ((BR - 1) * S + (K - 1) * dil + 1) * plane_pitch(W + 2 * pad, S) * sizeof(float);
     };
     while (band_bytes(nb) > 65536 && nb < Ho) ++nb;
     a.chunk = nb;
@@ -606,12 +609,15 @@ void dw_bwd_fill(std::vector<py::tuple>& calls, DwBwdBatch& bt, const int64_t* K
     check_f32(dw, "dw"); check_f32(dd, "dd"); check_f32(gout, "gout");
     DwBwdArgs& a = bt.e[i];
     a.N = x.size(0); a.C = x.size(1); a.H = x.size(2); a.W = x.size(3); a.Ho = dd.size(2); a.Wo = dd.size(3);
-    TORCH_CHECK(64 % a.Wo == 0 && a.Ho % (64 / a.Wo) == 0, "tile constraint");
     TORCH_CHECK(a.H == a.Ho * S && a.W == a.Wo * S, "dw_bwd needs H == Ho*S");
     TORCH_CHECK(gout.sizes() == x.sizes(), "gout shape");
     TORCH_CHECK(dw.numel() == a.C * K * K && dd.size(1) == a.C, "dw_bwd weight / grad shapes");
     a.x = x.data_ptr(); a.dw = dw.data_ptr<float>(); a.dd = dd.data_ptr<float>();
     a.gout = gout.data_ptr<float>(); a.gW = ptr_or_null<float>(gW); a.red = ptr_or_null<double>(red);
+    // the 64-pixel tile kernel needs whole tiles; layers the row-band plane kernels take (dw_plane_ok) do not
+    const bool plane = (a.C == 4 || a.C == 8 || (a.C % 16 == 0 && a.C <= kMaxC)) && a.Wo % 4 == 0 &&
+                       (((uintptr_t)a.x | (uintptr_t)a.dd | (uintptr_t)a.gout) & 15) == 0;
+    TORCH_CHECK(plane || (64 % a.Wo == 0 && a.Ho % (64 / a.Wo) == 0), "tile constraint");
     check_grad_sink(gW, (int64_t)a.C * K * K, gstride);
     a.gstride = gstride;
     a.overwrite = overwrite;

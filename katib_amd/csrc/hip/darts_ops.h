@@ -135,6 +135,7 @@ struct DwBwdArgs {
   int overwrite;  // non-PREBN: gout = masked grad (first writer of this input gradient) instead of +=
   int variant, nbands, nblk;  // dw_bwd_plane_multi_kernel: dw_bwd_variant, row bands, workgroups of this entry
   int vin = 0;  // dw_bwd_plane, stride 1: 4 input pixels per thread, 16-byte stores (host: vec_mask())
+  int blk0 = 0; // dw_bwd_plane_multi_kernel: first workgroup of this entry in the 1-D grid
 };
 constexpr int dw_bwd_variant(int K, int dil, int S, bool prebn) {
   return (((K == 5) * 4 + (dil == 2) * 2 + (S == 2)) << 1) | (prebn ? 1 : 0);

@@ -10,6 +10,7 @@
 #include <cstdlib>
 
 #include "darts_ops.h"
+#include "darts_plane_layout.h"
 
 namespace katib_hip {
 
@@ -62,14 +63,7 @@ enum StampKind { kStampDwBwd = 1, kStampDwPw = 2, kStampPoolBwd = 3, kStampPoolF
 // LDS cost a workgroup per CU.
 __host__ __device__ constexpr int plane_head_floats(int C) { return (C * 25 + C * C + 3) & ~3; }
 __host__ __device__ constexpr int dwb_head_floats(int C) { return (2 * C * 25 + 3) & ~3; }
-// Row pitch (floats) of the LDS planes the plane kernels stage (dwpw_plane, dw_bwd_plane): a
-// multiple of 4 floats, so the 4-pixel paths read every tap row as whole 16-byte ds_read_b128
-// quads from an aligned base (a lane's 4 outputs at stride 4 floats hit 8 of 32 banks as
-// 4-byte reads: 4-way conflicts), and an odd number of quads, so the lanes of one b128 lane
-// group that sit on consecutive rows start on different 16-byte bank slots.
-__host__ __device__ constexpr int lds_pitch(int w) {
-  return (((w + 3) & ~3) >> 2) & 1 ? ((w + 3) & ~3) : ((w + 3) & ~3) + 4;
-}
+// (row pitches and the lane maps of the staged planes: darts_plane_layout.h)
 // 4-pixels-per-thread output paths of the plane kernels (darts_ops.hip vec_mask())
 int vec_mask();
 

@@ -453,14 +453,15 @@ __device__ __forceinline__ void dw_bwd_plane_body(const DwBwdArgs& a, const int 
   const int BRi = H / nb, iy0 = band * BRi, nrow = BRi;
   const int oyA = (iy0 - PAD) >> SH;                 // floor division (S in {1, 2})
   const int oyB = (iy0 + nrow - 1 + PAD) >> SH;
-  const int ODR = oyB - oyA + 1, ODW = lds_pitch(Wo + 2 * PO), NP = nrow * W;  // row pitch: lds_pitch
+  // row pitches of the staged planes: darts_plane_layout.h (stride 1: tile_pitch for the tile map)
+  const int ODR = oyB - oyA + 1, ODW = plane_pitch(Wo + 2 * PO, S), PIN = plane_pitch(W, S), NP = nrow * W;
   const bool accum = !PREBN && !a.overwrite;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* sWt = smem;                    // [C][KK] depthwise weights (dwb_head_floats)
   float* sGW = smem + C * 25;           // [C][KK] block-local depthwise weight gradients
   float* sDD = smem + dwb_head_floats(C);  // [C][ODR][ODW]
-  float* sIn = sDD + C * ODR * ODW;     // [C][nrow][W] act(in)
-  float* sOld = sIn + C * NP;           // [C][nrow][W] current gradient (accumulate mode)
+  float* sIn = sDD + C * ODR * ODW;     // [C][nrow][PIN] act(in)
+  float* sOld = sIn + C * nrow * PIN;   // [C][nrow][PIN] current gradient (accumulate mode)
   __shared__ float sMean[C], sInv[C], sRed[2 * C];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   KSTAMP(0);
@@ -509,10 +510,10 @@ __device__ __forceinline__ void dw_bwd_plane_body(const DwBwdArgs& a, const int 
     }
   }
   {
-    const int q4 = NP / 4;
+    const int q4 = NP / 4, w4 = W / 4;
 #pragma unroll 4
     for (int i = tid; i < C * q4; i += 256) {
-      const int c = i / q4, o = (i - c * q4) * 4;
+      const int c = i / q4, oq = i - c * q4, o = oq * 4, r = oq / w4, lo = (c * nrow + r) * PIN + (oq - r * w4) * 4;
       float4 v = xval4<PREBN>(a.x, xn + ((size_t)c * H + iy0) * W + o);
       if (PREBN) {
         const float m = sMean[c], iv = sInv[c];
@@ -525,14 +526,14 @@ __device__ __forceinline__ void dw_bwd_plane_body(const DwBwdArgs& a, const int 
       v.y = fmaxf(v.y, 0.f);
       v.z = fmaxf(v.z, 0.f);
       v.w = fmaxf(v.w, 0.f);
-      *reinterpret_cast<float4*>(sIn + c * NP + o) = v;
+      *reinterpret_cast<float4*>(sIn + lo) = v;
     }
     if (accum) {
       const float* gsrc = a.gout + ((size_t)n * a.C + c0) * H * W;
 #pragma unroll 4
       for (int i = tid; i < C * q4; i += 256) {
-        const int c = i / q4, o = (i - c * q4) * 4;
-        *reinterpret_cast<float4*>(sOld + c * NP + o) =
+        const int c = i / q4, oq = i - c * q4, o = oq * 4, r = oq / w4;
+        *reinterpret_cast<float4*>(sOld + (c * nrow + r) * PIN + (oq - r * w4) * 4) =
             *reinterpret_cast<const float4*>(gsrc + ((size_t)c * H + iy0) * W + o);
       }
     }
@@ -544,24 +545,29 @@ __device__ __forceinline__ void dw_bwd_plane_body(const DwBwdArgs& a, const int 
 #pragma unroll
   for (int c = 0; c < C; ++c) st1[c] = st2[c] = 0.f;
   float* gn = a.gout + ((size_t)n * a.C + c0) * H * W;
-  if (S == 1 && a.vin) {
+  // The 4-pixel paths: stride 2 always, stride 1 through the tile map (widths of whole 2-quad cells);
+  // other widths take the pixel-per-thread loop below
+  const bool tiled = S == 1 && (W & 7) == 0;
+  const bool vin = a.vin && (S == 2 || tiled);
+  if (S == 1 && vin) {
     // stride 1: 4 consecutive input pixels of one row per thread (W % 4 == 0, as the staging
     // assumes): the taps' column offsets are shared, and the gradient leaves as one 16-byte store
     // per channel instead of four 4-byte ones
     // The staged dd row the 4 pixels meet through every column tap is dd columns ix .. ix + 3 + 2 PAD
-    // (PO = PAD at stride 1): NQ aligned 16-byte quads from ix (ODW = lds_pitch, a multiple of 4),
-    // read as ds_read_b128 per tap row instead of 4 K ds_read_b32 at a 4-float lane stride (8 of
-    // 32 banks: 4-way conflicts)
+    // (PO = PAD at stride 1): NQ aligned 16-byte quads from ix (ODW a multiple of 4), read as
+    // ds_read_b128 per tap row instead of 4 K ds_read_b32 at a 4-float lane stride
     typedef float f4 __attribute__((ext_vector_type(4)));
     constexpr int NQ = (4 + 2 * PAD + 3) / 4;
-    // work item = (channel, pixel quad), channel-major: with the channel loop inside the thread
-    // only NP / 4 threads had work (64 of 256 for an 8-row band of a 32-wide plane), each walking
-    // C channels with nothing to hide its LDS latency behind; now every thread takes one item and a
-    // wave holds one channel whenever NP / 4 is a multiple of 64 (uniform weight reads)
-    const int NQ4 = NP / 4;
-    for (int j = tid; j < ((dbg & 1) ? 0 : C * NQ4); j += 256) {
-      const int c = j / NQ4, p = (j - c * NQ4) * 4;
-      const int r = p / W, ix = p - r * W, iy = iy0 + r;
+    // work item = (channel, pixel quad), one per thread and pass, laid out by the tile map of
+    // darts_plane_layout.h: every ds_read_b128 lane group holds 8 rows x 2 adjacent quads of one
+    // channel, which tile_pitch makes conflict-free for the dd tap rows and the act(in) read alike
+    // (in row-major quad order a lane group held half rows of 4 different rows, two of which
+    // always overlapped: 2-3 LDS cycles per read instead of 1). Rows past a short band's end idle.
+    const int npair = W >> 3, nrb = (nrow + kCellRows - 1) / kCellRows;
+    for (int j = 4 * wave + tile_cell(lane); j < ((dbg & 1) ? 0 : C * nrb * npair); j += kBlockCells) {
+      const TileItem it = tile_item(j, lane, nrb, npair);
+      if (it.row >= nrow) continue;
+      const int c = it.c, r = it.row, ix = 4 * it.quad, iy = iy0 + r;
       int srow[K];
 #pragma unroll
       for (int k = 0; k < K; ++k) srow[k] = (iy + PAD - k * DIL - oyA) * ODW + ix;
@@ -590,7 +596,7 @@ __device__ __forceinline__ void dw_bwd_plane_body(const DwBwdArgs& a, const int 
           ga.w += w * v[o + 3];
         }
       }
-      const int li = (c * nrow + r) * W + ix;
+      const int li = (c * nrow + r) * PIN + ix;
       const f4 act = *reinterpret_cast<const f4*>(sIn + li);
       const f4 g = {act.x > 0.f ? ga.x : 0.f, act.y > 0.f ? ga.y : 0.f, act.z > 0.f ? ga.z : 0.f,
                     act.w > 0.f ? ga.w : 0.f};
@@ -617,7 +623,7 @@ __device__ __forceinline__ void dw_bwd_plane_body(const DwBwdArgs& a, const int 
     // wave-uniform and the others are skipped by scalar branches instead of masked multiply-adds:
     // a quarter of the work (a dilated tap set is all-or-nothing per class).
     const int hw2 = W / 2, NPc = (nrow / 2) * hw2;
-    for (int q = tid; q < ((dbg & 1) || !a.vin ? 0 : NP); q += 256) {
+    for (int q = tid; q < ((dbg & 1) || !vin ? 0 : NP); q += 256) {
       const int cls = NPc % 64 == 0 ? __builtin_amdgcn_readfirstlane(q / NPc) : q / NPc;
       const int qq = q - cls * NPc, rr = qq / hw2, xx = qq - rr * hw2;
       const int r = 2 * rr + (cls >> 1), ix = 2 * xx + (cls & 1), iy = iy0 + r;
@@ -643,7 +649,7 @@ __device__ __forceinline__ void dw_bwd_plane_body(const DwBwdArgs& a, const int 
             ga += wk[ky * K + kx] * dd[srow[ky] + scol[kx]];
           }
         }
-        const int li = (c * nrow + r) * W + ix;
+        const int li = (c * nrow + r) * PIN + ix;
         const float act = sIn[li];
         const size_t gi = ((size_t)c * H + iy) * W + ix;
         const float g = act > 0.f ? ga : 0.f;
@@ -657,7 +663,7 @@ __device__ __forceinline__ void dw_bwd_plane_body(const DwBwdArgs& a, const int 
       }
     }
   }
-  for (int p = tid; p < ((dbg & 1) || a.vin ? 0 : NP); p += 256) {
+  for (int p = tid; p < ((dbg & 1) || vin ? 0 : NP); p += 256) {
     const int r = p / W, ix = p - r * W, iy = iy0 + r;
     int srow[K], scol[K];
     float mrow[K], mcol[K];
@@ -685,7 +691,7 @@ __device__ __forceinline__ void dw_bwd_plane_body(const DwBwdArgs& a, const int 
         }
         ga += S == 1 ? rowacc : mrow[ky] * rowacc;
       }
-      const int li = (c * nrow + r) * W + ix;
+      const int li = (c * nrow + r) * PIN + ix;
       const float act = sIn[li];
       const size_t gi = ((size_t)c * H + iy) * W + ix;
       const float g = act > 0.f ? ga : 0.f;
@@ -707,46 +713,66 @@ __device__ __forceinline__ void dw_bwd_plane_body(const DwBwdArgs& a, const int 
   }
   KSTAMP(3);
   // depthwise weight gradients over the band: thread per (channel, tap, pixel part)
-  if (a.gW && !(dbg & 2) && S == 1) {
-    // stride 1: job = (channel, ky, own row). A 4-pixel quad of the input row (one 16-byte LDS
-    // read) and the 4 + 2*PAD dd values it meets across all K column taps (registers) feed
-    // 4*K multiply-adds: ~1.5 per LDS read against 0.5 for a pixel-by-pixel walk per tap
-    // job = (row part, channel, ky, row); when the C * K * nrow jobs leave threads idle, each row
-    // is split into XP column parts (XP | W / 4), a partial sum each
-    const int JB = C * K * nrow, W4 = W / 4;
-    int XP = 1;
-    while (XP * 2 * JB <= 256 && W4 % (XP * 2) == 0) XP *= 2;
-    const int XW = W / XP;
-    for (int j = tid; j < JB * XP; j += 256) {
-      const int xp = j / JB, jj = j - xp * JB;
-      const int c = jj / (K * nrow), rem = jj - c * K * nrow, ky = rem / nrow, r = rem - ky * nrow;
-      const float* ddr = sDD + (c * ODR + iy0 + r + PAD - ky * DIL - oyA) * ODW + PO;
-      const float* inr = sIn + c * NP + r * W;
-      float acc[K];
+  if (a.gW && !(dbg & 2) && tiled) {
+    // stride 1: job = (channel, ky, own row, column part). A 4-pixel quad of the input row (one
+    // 16-byte LDS read) and the 4 + 2*PAD dd values it meets across all K column taps (registers)
+    // feed 4*K multiply-adds: ~1.5 per LDS read against 0.5 for a pixel-by-pixel walk per tap.
+    // Jobs are laid out in the cells of the tile map (wgrad_job: 8 rows x 2 interleaved column
+    // parts per ds_read_b128 lane group), so both reads of every step are conflict-free - with one
+    // lane per row the act(in) reads of 16 rows sat on 2 of the 16 bank slots (8-way) - and the
+    // row is split further between cells until the jobs fill whole 16-cell passes. The K partial
+    // sums are reduced across the lanes that share (channel, ky) before they touch sGW: one LDS
+    // atomic per wave and weight when the wave's 4 cells share them, else one per cell (a
+    // same-address ds_add_f32 per lane serialises 64-fold).
+    constexpr int KP = K == 3 ? 4 : 8;  // K accumulators padded to a power of two (reduce-scatter)
+    const int npair = W >> 3, nrb = (nrow + kCellRows - 1) / kCellRows;
+    const int xp = wgrad_parts(C * K * nrb, npair), ncell = C * K * nrb * xp;
+    const bool wave_job = ((nrb * xp) & 3) == 0;  // the 4 cells of a wave share (channel, ky)
+    for (int u0 = 4 * wave; u0 < ncell; u0 += kBlockCells) {
+      const int u = u0 + tile_cell(lane);
+      const WgradJob jb = wgrad_job(u, lane, K, nrb, xp);
+      float acc[KP];
 #pragma unroll
-      for (int kx = 0; kx < K; ++kx) acc[kx] = 0.f;
-      for (int ix = xp * XW; ix < (xp + 1) * XW; ix += 4) {
-        const float4 v = *reinterpret_cast<const float4*>(inr + ix);
-        // dseg[m] = dd[ix - PAD + m]: dd column ix - PAD + PO + m = ix + m (PO = PAD at stride 1),
-        // whole aligned quads from ix (ds_read_b128; ODW = lds_pitch)
-        constexpr int NQ = (4 + 2 * PAD + 3) / 4;
-        float dseg[4 * NQ];
+      for (int kx = 0; kx < KP; ++kx) acc[kx] = 0.f;
+      if (u < ncell && jb.row < nrow) {
+        // dd columns ix .. ix + 3 + 2 PAD of the tap row (PO = PAD at stride 1), whole aligned quads
+        const float* ddr = sDD + (jb.c * ODR + iy0 + jb.row + PAD - jb.ky * DIL - oyA) * ODW;
+        const float* inr = sIn + (jb.c * nrow + jb.row) * PIN;
+        for (int ix = 4 * jb.q0; ix < W; ix += 8 * xp) {
+          const float4 v = *reinterpret_cast<const float4*>(inr + ix);
+          constexpr int NQ = (4 + 2 * PAD + 3) / 4;
+          float dseg[4 * NQ];  // dseg[m] = dd[ix - PAD + m]
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-          const float4 t = *reinterpret_cast<const float4*>(ddr - PO + ix + 4 * q);
-          dseg[4 * q] = t.x;
-          dseg[4 * q + 1] = t.y;
-          dseg[4 * q + 2] = t.z;
-          dseg[4 * q + 3] = t.w;
-        }
+          for (int q = 0; q < NQ; ++q) {
+            const float4 t = *reinterpret_cast<const float4*>(ddr + ix + 4 * q);
+            dseg[4 * q] = t.x;
+            dseg[4 * q + 1] = t.y;
+            dseg[4 * q + 2] = t.z;
+            dseg[4 * q + 3] = t.w;
+          }
 #pragma unroll
-        for (int kx = 0; kx < K; ++kx) {
-          const int o = 2 * PAD - kx * DIL;  // in[ix + q] meets dd[ix + q + PAD - kx*DIL]
-          acc[kx] += v.x * dseg[o] + v.y * dseg[o + 1] + v.z * dseg[o + 2] + v.w * dseg[o + 3];
+          for (int kx = 0; kx < K; ++kx) {
+            const int o = 2 * PAD - kx * DIL;  // in[ix + q] meets dd[ix + q + PAD - kx*DIL]
+            acc[kx] += v.x * dseg[o] + v.y * dseg[o + 1] + v.z * dseg[o + 2] + v.w * dseg[o + 3];
+          }
         }
       }
+      float* gw = sGW + jb.c * KK + jb.ky * K;
+      if (wave_job) {  // ncell is a multiple of 4 here: every cell of the wave is a job
+        const float sum = wave_reduce_scatter<KP>(acc);
+        const int kx = wave_scatter_index<KP>(lane);
+        if ((lane & (64 / KP - 1)) == 0 && kx < K) atomicAdd(gw + kx, sum);
+      } else {
 #pragma unroll
-      for (int kx = 0; kx < K; ++kx) atomicAdd(sGW + c * KK + ky * K + kx, acc[kx]);
+        for (int kx = 0; kx < K; ++kx) {
+          float v = acc[kx];  // the 16 lanes of a cell: lane bits 0, 1 and (2 with 3), (2 with 4)
+          v += __shfl_xor(v, 1, 64);
+          v += __shfl_xor(v, 2, 64);
+          v += __shfl_xor(v, 12, 64);
+          v += __shfl_xor(v, 20, 64);
+          if ((lane & 27) == 0 && u < ncell) atomicAdd(gw + kx, v);
+        }
+      }
     }
   } else if (a.gW && !(dbg & 2)) {
     constexpr int JOBS = C * KK, T = JOBS >= 256 ? 1 : 256 / JOBS;
@@ -754,13 +780,13 @@ __device__ __forceinline__ void dw_bwd_plane_body(const DwBwdArgs& a, const int 
       const int job = j / T, part = j - job * T;
       const int c = job / KK, tap = job - c * KK, ky = tap / K, kx = tap - ky * K;
       const float* dd = sDD + c * ODR * ODW;
-      const float* in = sIn + c * NP;
+      const float* in = sIn + c * nrow * PIN;
       float acc = 0.f;
       for (int r = 0; r < nrow; ++r) {
         const int t = iy0 + r + PAD - ky * DIL;
         if (S == 2 && (t & 1)) continue;
         const float* ddr = dd + ((t >> SH) - oyA) * ODW + PO;
-        const float* inr = in + r * W;
+        const float* inr = in + r * PIN;
         for (int ix = part * S + ((S == 2) ? ((PAD - kx * DIL) & 1) : 0); ix < W; ix += T * S)
           acc += inr[ix] * ddr[(ix + PAD - kx * DIL) >> SH];
       }
@@ -770,9 +796,9 @@ __device__ __forceinline__ void dw_bwd_plane_body(const DwBwdArgs& a, const int 
   KSTAMP(4);
   __syncthreads();
   if (PREBN && a.red && tid < 2 * C)  // red replica layout [sum g: a.C | sum g*y: a.C]
-    atomicAdd(a.red + rep_slot() * 2 * a.C + (tid < C ? c0 + tid : a.C + c0 + tid - C), (double)sRed[tid]);
-  if (a.gW)
-    for (int i = tid; i < C * KK; i += 256) atomicAdd(a.gW + (size_t)rep_slot() * a.gstride + c0 * KK + i, sGW[i]);
+    atomicAdd(a.red + (bx % kRep) * 2 * a.C + (tid < C ? c0 + tid : a.C + c0 + tid - C), (double)sRed[tid]);
+  if (a.gW)  // replica slot: the entry-local workgroup index (a mixed launch's grid is the entries' sum)
+    for (int i = tid; i < C * KK; i += 256) atomicAdd(a.gW + (size_t)(bx % kRep) * a.gstride + c0 * KK + i, sGW[i]);
   KSTAMP(5);
 }
 
@@ -788,17 +814,22 @@ __global__ void __launch_bounds__(256) dw_bwd_plane_kernel(DwBwdBatch bt, int nb
 // (masked) input-gradient buffer that the pool backward then sums into gx. Each entry carries
 // its variant (dw_bwd_variant), band count and workgroup count.
 #define DWB_CASE(KK, DD, SS, PB) \
-  case dw_bwd_variant(KK, DD, SS, PB): dw_bwd_plane_body<KK, DD, SS, PB, C>(a, blockIdx.x, a.nbands, 0); break;
+  case dw_bwd_variant(KK, DD, SS, PB): dw_bwd_plane_body<KK, DD, SS, PB, C>(a, bx, a.nbands, 0); break;
 template <int C>
 __global__ void __launch_bounds__(256) dw_bwd_plane_multi_kernel(DwBwdBatch bt) {
-  const DwBwdArgs a = bt.e[blockIdx.y];  // copy: see dwpw_plane_multi_kernel
-  if ((int)blockIdx.x < a.nblk) {
-    switch (a.variant) {
-      DWB_CASE(3, 1, 1, true) DWB_CASE(5, 1, 1, true)
-      DWB_CASE(3, 1, 1, false) DWB_CASE(3, 1, 2, false) DWB_CASE(5, 1, 1, false) DWB_CASE(5, 1, 2, false)
-      DWB_CASE(3, 2, 1, false) DWB_CASE(3, 2, 2, false) DWB_CASE(5, 2, 1, false) DWB_CASE(5, 2, 2, false)
-      default: break;
-    }
+  // 1-D grid of exactly the entries' workgroups: entry i owns [blk0, blk0 + nblk) (a
+  // max-workgroups x entries grid started a workgroup, with its LDS, for every slot an entry
+  // with fewer bands left empty)
+  int ei = 0;
+  for (int i = 1; i < bt.n; ++i)
+    if ((int)blockIdx.x >= bt.e[i].blk0) ei = i;
+  const DwBwdArgs a = bt.e[ei];  // copy: see dwpw_plane_multi_kernel
+  const int bx = blockIdx.x - a.blk0;  // entry-local workgroup (band, group, replica slot)
+  switch (a.variant) {
+    DWB_CASE(3, 1, 1, true) DWB_CASE(5, 1, 1, true)
+    DWB_CASE(3, 1, 1, false) DWB_CASE(3, 1, 2, false) DWB_CASE(5, 1, 1, false) DWB_CASE(5, 1, 2, false)
+    DWB_CASE(3, 2, 1, false) DWB_CASE(3, 2, 2, false) DWB_CASE(5, 2, 1, false) DWB_CASE(5, 2, 2, false)
+    default: break;
   }
   if (bt.tail.ctr) fold_tail(bt.tail);
 }
@@ -1117,13 +1148,21 @@ void launch_pool_bwd_multi(const PoolBwdBatch& b, hipStream_t st) {
   KSTAMP_DISARM(st)
 }
 
+// LDS budget (KB) of one dw_bwd_plane band: the launchers cut an image into more bands until a
+// band fits. With the stride-1 tile pitches a whole 32 x 32 plane of 4 channels takes 43 KB (3x3)
+// to 47 KB (5x5, dilated): 40 cuts every such entry into two 16-row bands of 22-25 KB (6 resident
+// workgroups per CU), 48 keeps them whole (3 per CU, no halo rows staged twice).
+#ifndef KATIB_DWB_BAND_KB
+#define KATIB_DWB_BAND_KB 48
+#endif
+constexpr int kDwbBandKB = KATIB_DWB_BAND_KB;
 // LDS floats of one dw_bwd_plane band (nb bands per image)
 static size_t dw_plane_floats(const DwBwdArgs& a, int K, int DIL, int S, int nb, bool accum, int C) {
   const int PAD = (K - 1) / 2 * DIL, PO = (PAD + S - 1) / S, sh = S == 2 ? 1 : 0, BRi = a.H / nb;
   auto fdiv = [sh](int v) { return v >= 0 ? v >> sh : -((-v + (1 << sh) - 1) >> sh); };
   const int ODR = fdiv(BRi - 1 + PAD) - fdiv(-PAD) + 2;  // +1: odd bands start at odd rows
-  return (size_t)dwb_head_floats(C) + (size_t)C * ODR * lds_pitch(a.Wo + 2 * PO) +
-         (size_t)C * BRi * a.W * (accum ? 2 : 1);
+  return (size_t)dwb_head_floats(C) + (size_t)C * ODR * plane_pitch(a.Wo + 2 * PO, S) +
+         (size_t)C * BRi * plane_pitch(a.W, S) * (accum ? 2 : 1);
 }
 
 template <int K, int DIL, int S, int C>
@@ -1132,11 +1171,11 @@ static void launch_dw_bwd_plane_t(const DwBwdBatch& b, bool prebn, hipStream_t s
   bool accum = false;
   for (int i = 0; i < b.n; ++i) accum |= !prebn && !b.e[i].overwrite;
   // bands: as few as possible (less halo) while the launch still has ~4 workgroups per CU and a
-  // band stays within 40 KB of LDS
+  // band stays within kDwbBandKB of LDS
   int nb = 1;
   const int G = a.C / C;  // channel groups per image
   while (nb < 8 && a.H % (2 * nb) == 0 &&
-         (dw_plane_floats(a, K, DIL, S, nb, accum, C) * 4 > 40 * 1024 || a.N * nb * G * b.n < 1024))
+         (dw_plane_floats(a, K, DIL, S, nb, accum, C) * 4 > kDwbBandKB * 1024 || a.N * nb * G * b.n < 1024))
     nb *= 2;
   const size_t lds = sizeof(float) * dw_plane_floats(a, K, DIL, S, nb, accum, C);
   dim3 grid(a.N * nb * G, b.n);
@@ -1188,7 +1227,7 @@ bool launch_dw_bwd_multi(DwBwdBatch b, hipStream_t st) {
   constexpr int grp = 4;
   const int C = (a0.C == 4 || grp == 4) ? 4 : 8;  // channel groups as launch_dw_bwd_t
   if (a0.C % C) return false;
-  int maxblk = 0;
+  int total = 0;
   size_t lds = 0;
   for (int i = 0; i < b.n; ++i) {
     DwBwdArgs& a = b.e[i];
@@ -1202,17 +1241,18 @@ bool launch_dw_bwd_multi(DwBwdBatch b, hipStream_t st) {
     const int G = a.C / C;
     constexpr int min_wg = 512;
     while (nb < 8 && a.H % (2 * nb) == 0 &&
-           (dw_plane_floats(a, K, DIL, S, nb, false, C) * 4 > 40 * 1024 || a.N * nb * G * b.n < min_wg))
+           (dw_plane_floats(a, K, DIL, S, nb, false, C) * 4 > kDwbBandKB * 1024 || a.N * nb * G * b.n < min_wg))
       nb *= 2;
     a.nbands = nb;
     a.nblk = a.N * nb * G;
     a.vin = S == 1 ? (vec_mask() >> (C == 4 ? 2 : 3)) & 1 : (vec_mask() >> 4) & 1;
-    maxblk = std::max(maxblk, a.nblk);
+    a.blk0 = total;  // the entries' workgroups back to back in a 1-D grid
+    total += a.nblk;
     lds = std::max(lds, sizeof(float) * dw_plane_floats(a, K, DIL, S, nb, false, C));
   }
   KSTAMP_ARM(kStampDwBwd, st)
-  if (C == 4) hipLaunchKernelGGL(dw_bwd_plane_multi_kernel<4>, dim3(maxblk, b.n), dim3(256), lds, st, b);
-  else hipLaunchKernelGGL(dw_bwd_plane_multi_kernel<8>, dim3(maxblk, b.n), dim3(256), lds, st, b);
+  if (C == 4) hipLaunchKernelGGL(dw_bwd_plane_multi_kernel<4>, dim3(total), dim3(256), lds, st, b);
+  else hipLaunchKernelGGL(dw_bwd_plane_multi_kernel<8>, dim3(total), dim3(256), lds, st, b);
   KSTAMP_DISARM(st)
   return true;
 }

@@ -151,7 +151,7 @@ __device__ __forceinline__ void dwpw_plane_body(const DwPwFwdArgs& a, const int 
   const int G = PW ? 1 : a.C / C, c0 = PW ? 0 : (bx % G) * C, nbx = PW ? bx : bx / G;
   const int n = nbx / nb, band = nbx - n * nb;
   const int oy0 = band * BR, oy1 = min(Ho, oy0 + BR);
-  const int HP = (BR - 1) * S + (K - 1) * DIL + 1, WP = lds_pitch(W + 2 * pad), PL = HP * WP;
+  const int HP = (BR - 1) * S + (K - 1) * DIL + 1, WP = plane_pitch(W + 2 * pad, S), PL = HP * WP;
   const int iyb = oy0 * S - pad;  // input row of staged row 0
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* sWt = smem;                            // [C][KK] depthwise weights (plane_head_floats)
@@ -238,11 +238,25 @@ __device__ __forceinline__ void dwpw_plane_body(const DwPwFwdArgs& a, const int 
     // 4 consecutive output pixels (one row: Wo % 4 == 0) per thread: d and z leave as one 16-byte
     // (bf16: 8-byte) store per channel instead of four 4-byte ones. Each tap row the 4 outputs
     // reach (SPAN staged columns from ox0 * S, a multiple of 4) is read as NQ aligned 16-byte
-    // quads (WP = lds_pitch: a multiple of 4 floats, wide enough for the last quad): 2-4
+    // quads (WP = plane_pitch: a multiple of 4 floats, wide enough for the last quad): 2-4
     // ds_read_b128 per row instead of 4 K ds_read_b32 whose lanes, 4 S floats apart, sat on 8 (S = 1)
     // or 4 (S = 2) of the 32 banks
     constexpr int SPAN = 3 * S + (K - 1) * DIL + 1, NQ = (SPAN + 3) / 4;
-    for (int p = oy0 * Wo + 4 * tid; p < oy1 * Wo; p += 1024) {
+    // Stride 1, widths of whole 2-quad cells: the quads are dealt to the lanes by the tile map of
+    // darts_plane_layout.h (a ds_read_b128 lane group = 8 rows x 2 adjacent quads), which with
+    // tile_pitch makes every tap-row read conflict-free; in row-major quad order a lane group held
+    // half rows of 4 different rows, two of which always overlapped (2-3 LDS cycles per read).
+    // Other widths and stride 2 keep the row-major order.
+    const bool tiled = S == 1 && (Wo & 7) == 0;
+    const int nrowo = oy1 - oy0, npair = Wo >> 3, nrb = (nrowo + kCellRows - 1) / kCellRows;
+    const int nit = tiled ? nrb * npair : nrowo * Wo / 4;  // cells / quads
+    for (int j = tiled ? 4 * wave + tile_cell(lane) : tid; j < nit; j += tiled ? kBlockCells : 256) {
+      int p = oy0 * Wo + 4 * j;
+      if (tiled) {
+        const TileItem it = tile_item(j, lane, nrb, npair);  // it.c == 0: the thread owns all channels
+        if (it.row >= nrowo) continue;
+        p = (oy0 + it.row) * Wo + 4 * it.quad;
+      }
       const int oy = p / Wo, ox0 = p - oy * Wo;
       zf4 d[C];
 #pragma unroll
