@@ -88,6 +88,18 @@ hipError_t attn_fwd(const bf16* qkv, bf16* o, float* lse, int B, int T, int H, f
 // dqkv [B, T, 3, H, 64] bf16 (fully written); delta [B, H, T] fp32 scratch.
 hipError_t attn_bwd(const bf16* qkv, const bf16* o, const bf16* dout, const float* lse, float* delta, bf16* dqkv,
                     int B, int T, int H, float sm_scale, hipStream_t st);
+// With dropout of the attention probabilities P [B*H, T, T] (the mask is recomputed, never stored):
+// O = (keep * scale * P) V, lse that of the undropped softmax; dV = (keep * scale * P)^T dO,
+// dS = P (keep * scale * dP - delta). 8-bit draws on 4 x 4 tiles, one Philox call per 16 elements:
+//   blk = (bh * T/4 + (q >> 2)) * T/4 + (k >> 2) (64-bit), bh = b * H + h;
+//   w = Philox4x32-10(counter = (blk lo, blk hi, site, step), key = (seed lo, seed hi));
+//   element (q, k) is kept iff ((w[q & 3] >> 8 (k & 3)) & 0xff) >= thr8.
+// drop.thr carries thr8 = floor(256 p + 0.5) in 1..255 and drop.scale = 256 / (256 - thr8); the draw of
+// a causally masked position is never used. hipErrorInvalidValue for thr8 = 0 (use the calls above).
+hipError_t attn_fwd(const bf16* qkv, bf16* o, float* lse, int B, int T, int H, float sm_scale, const DropSpec& drop,
+                    hipStream_t st);
+hipError_t attn_bwd(const bf16* qkv, const bf16* o, const bf16* dout, const float* lse, float* delta, bf16* dqkv,
+                    int B, int T, int H, float sm_scale, const DropSpec& drop, hipStream_t st);
 
 }  // namespace tfm
 }  // namespace katib_hip

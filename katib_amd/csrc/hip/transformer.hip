@@ -20,9 +20,13 @@
 //                           cross-lane steps, and the bf16 probabilities feed the P.V
 //                           MFMA as B operands with no data movement; V (and K, dO, Q in
 //                           the backward) are consumed column-wise through the gfx950
-//                           transposing LDS read ds_read_b64_tr_b16.
+//                           transposing LDS read ds_read_b64_tr_b16. The <true> instantiations
+//                           drop attention probabilities: the keep mask is recomputed from
+//                           Philox in each kernel's own lane layout (see "attention-probability
+//                           dropout" below), never stored.
 #include <cstdlib>
 #include "transformer.h"
+#include "philox.h"
 
 #include <math.h>
 
@@ -698,10 +702,67 @@ struct TileLoader {
   }
 };
 
+// ---- attention-probability dropout (the DROP = true instantiations of the three kernels below)
+// Contract (transformer.h, ops/transformer.py attn_dropout_mask): P [BH, T, T] is cut into 4 x 4
+// tiles, tile (bh, q >> 2, k >> 2) has the 64-bit index blk = (bh * T/4 + (q >> 2)) * T/4 + (k >> 2)
+// and draws w = Philox4x32-10((blk lo, blk hi, site, step), seed); element (q, k) takes byte k & 3
+// of word w[q & 3] and is kept iff byte >= thr8. One call serves 16 probabilities.
+//
+// In all three kernels lanes 4a .. 4a + 3 of a 16-lane group (a DPP quad) hold, for each of the
+// four 16-wide MFMA tiles n of a 64-wide LDS tile, a 4 x 4 block of P that is exactly one contract
+// tile: in attn_fwd_k / attn_dq_k queries 4a .. 4a + 3 (one per lane) by keys 16 n + 4 g + 0..3 (the
+// lane's four accumulator rows), in attn_dkdv_k keys 4a .. 4a + 3 (one per lane) by queries
+// 16 n + 4 g + 0..3. Lane m of the quad makes the one Philox call of tile n = m and the quad hands
+// the words round with quad_perm DPP moves - no LDS, no wave-wide shuffle.
+template <int K>  // the value lane K of the quad holds
+__device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, K * 0x55, 0xf, 0xf, true);
+}
+// row4 = bh * T/4 + (q >> 2) (fits 32 bits: B * H * T < 2^31 / 192, transformer_bind.cpp check_attn)
+__device__ __forceinline__ u32x4 attn_tile_words(uint32_t row4, uint32_t T4, uint32_t k4, const DropSpec& drop,
+                                                 uint32_t step) {
+  const uint64_t blk = (uint64_t)row4 * T4 + k4;
+  return philox4x32_10(u32x4{(uint32_t)blk, (uint32_t)(blk >> 32), drop.site, step}, (uint32_t)drop.seed,
+                       (uint32_t)(drop.seed >> 32));
+}
+// Query-on-the-lane layout: lane m = li & 3 holds the words of tile n = m; it needs, for every tile n,
+// the word of its own query (w[m]) from lane n: a 4 x 4 transpose across the quad. x[n] covers keys
+// 16 n + 4 g + 0..3 in its bytes 0..3.
+__device__ __forceinline__ u32x4 quad_transpose(const u32x4& w, int m) {
+  u32x4 x;
+#define KATIB_QT_ROW(N)                                                                 \
+  {                                                                                     \
+    const uint32_t a0 = quad_bcast<N>(w[0]), a1 = quad_bcast<N>(w[1]), a2 = quad_bcast<N>(w[2]), \
+                   a3 = quad_bcast<N>(w[3]);                                            \
+    x[N] = m == 0 ? a0 : (m == 1 ? a1 : (m == 2 ? a2 : a3));                            \
+  }
+  KATIB_QT_ROW(0) KATIB_QT_ROW(1) KATIB_QT_ROW(2) KATIB_QT_ROW(3)
+#undef KATIB_QT_ROW
+  return x;
+}
+// Key-on-the-lane layout (attn_dkdv_k): the four words of quad lane n, n a constant of an unrolled loop.
+__device__ __forceinline__ u32x4 quad_bcast4(const u32x4& w, int n) {
+  switch (n) {
+    case 0: return u32x4{quad_bcast<0>(w[0]), quad_bcast<0>(w[1]), quad_bcast<0>(w[2]), quad_bcast<0>(w[3])};
+    case 1: return u32x4{quad_bcast<1>(w[0]), quad_bcast<1>(w[1]), quad_bcast<1>(w[2]), quad_bcast<1>(w[3])};
+    case 2: return u32x4{quad_bcast<2>(w[0]), quad_bcast<2>(w[1]), quad_bcast<2>(w[2]), quad_bcast<2>(w[3])};
+    default: return u32x4{quad_bcast<3>(w[0]), quad_bcast<3>(w[1]), quad_bcast<3>(w[2]), quad_bcast<3>(w[3])};
+  }
+}
+__device__ __forceinline__ bool keep8(uint32_t word, int j, uint32_t thr8) {
+  return ((word >> (8 * j)) & 0xffu) >= thr8;
+}
+
 // grid: (T / QB) * B * H blocks, heaviest (last) query blocks first; block -> bh = id % BH
 // keeps all query blocks of one (batch, head) on one XCD group when BH % 8 == 0 (K/V in one L2).
-__global__ __launch_bounds__(256) void attn_fwd_k(const u16* __restrict__ qkv, u16* __restrict__ o,
-                                                  float* __restrict__ lse, int T, int H, int BH, float c) {
+// DROP: O = (keep * scale * P) V; the row sum and lse stay those of the undropped softmax, and scale
+// goes into the output normalisation. Left alone the <true> instantiation takes 172 VGPRs, 4 over the
+// 168 of three waves per SIMD that the plain kernel (160) runs at, so it asks for three; <false> gets
+// the default range and compiles as it did without the attribute.
+template <bool DROP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DROP ? 3 : 1, DROP ? 3 : 8)))
+void attn_fwd_k(const u16* __restrict__ qkv, u16* __restrict__ o, float* __restrict__ lse, int T, int H, int BH,
+                float c, const DropSpec drop) {
   __shared__ __align__(16) u16 sm[2][2][KT * LDK];
   const int nqb = T / QB;
   const int bh = blockIdx.x % BH, qb = nqb - 1 - blockIdx.x / BH;
@@ -724,6 +785,8 @@ __global__ __launch_bounds__(256) void attn_fwd_k(const u16* __restrict__ qkv, u
   for (int r = 0; r < 2; ++r)
 #pragma unroll
     for (int mm = 0; mm < 4; ++mm) acc[r][mm] = f32x4{0.f, 0.f, 0.f, 0.f};
+  [[maybe_unused]] uint32_t step = 0;
+  if constexpr (DROP) step = (uint32_t)*drop.step;
 
   const int ntiles = (q0 + QB) / KT;
   TileLoader ld;
@@ -794,6 +857,17 @@ __global__ __launch_bounds__(256) void attn_fwd_k(const u16* __restrict__ qkv, u
 #pragma unroll
           for (int mm = 0; mm < 4; ++mm) acc[r][mm] *= alpha;
         }
+        if constexpr (DROP) {
+          const u32x4 x = quad_transpose(
+              attn_tile_words((uint32_t)(bh * (T >> 2) + (q >> 2)), (uint32_t)(T >> 2),
+                              (uint32_t)((kv0 >> 2) + 4 * (li & 3) + g), drop, step),
+              li & 3);
+#pragma unroll
+          for (int n = 0; n < 4; ++n)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              if (!keep8(x[n], j, drop.thr)) s[r][n][j] = 0.f;
+        }
         pb[r][0] = pack8(s[r][0], s[r][1]);
         pb[r][1] = pack8(s[r][2], s[r][3]);
       }
@@ -812,7 +886,8 @@ __global__ __launch_bounds__(256) void attn_fwd_k(const u16* __restrict__ qkv, u
 #pragma unroll
   for (int r = 0; r < 2; ++r) {
     const int q = q0w + 16 * r + li;
-    const float inv = 1.f / lrow[r];
+    float inv = 1.f / lrow[r];
+    if constexpr (DROP) inv *= drop.scale;
     u16* orow = o + ((int64_t)(b * T + q) * H + h) * HD;
 #pragma unroll
     for (int mm = 0; mm < 4; ++mm)
@@ -843,10 +918,12 @@ __global__ __launch_bounds__(256) void attn_delta_k(const u16* __restrict__ o, c
 }
 
 // dQ: per query block (like the forward), S^T and dP^T with the query on the lane.
+// DROP: dS = P (keep * scale * dP - delta), the mask in the forward's lane layout.
+template <bool DROP>
 __global__ __launch_bounds__(256) void attn_dq_k(const u16* __restrict__ qkv, const u16* __restrict__ dout,
                                                  const float* __restrict__ lse, const float* __restrict__ delta,
                                                  u16* __restrict__ dqkv, int T, int H, int BH, float c,
-                                                 float sm_scale) {
+                                                 float sm_scale, const DropSpec drop) {
   __shared__ __align__(16) u16 sm[2][2][KT * LDK];
   const int nqb = T / QB;
   const int bh = blockIdx.x % BH, qb = nqb - 1 - blockIdx.x / BH;
@@ -875,6 +952,8 @@ __global__ __launch_bounds__(256) void attn_dq_k(const u16* __restrict__ qkv, co
   for (int r = 0; r < 2; ++r)
 #pragma unroll
     for (int mm = 0; mm < 4; ++mm) acc[r][mm] = f32x4{0.f, 0.f, 0.f, 0.f};
+  [[maybe_unused]] uint32_t step = 0;
+  if constexpr (DROP) step = (uint32_t)*drop.step;
 
   const int ntiles = (q0 + QB) / KT;
   TileLoader ld;
@@ -909,13 +988,21 @@ __global__ __launch_bounds__(256) void attn_dq_k(const u16* __restrict__ qkv, co
 #pragma unroll
       for (int r = 0; r < 2; ++r) {
         const int q = q0w + 16 * r + li;
+        [[maybe_unused]] u32x4 x;
+        if constexpr (DROP)
+          x = quad_transpose(attn_tile_words((uint32_t)(bh * (T >> 2) + (q >> 2)), (uint32_t)(T >> 2),
+                                             (uint32_t)((kv0 >> 2) + 4 * (li & 3) + g), drop, step),
+                             li & 3);
 #pragma unroll
         for (int n = 0; n < 4; ++n)
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r][n][j], c, -lq[r]));  // v_exp_f32, see attn_fwd_k
             if (diag && kv0 + 16 * n + 4 * g + j > q) p = 0.f;
-            s[r][n][j] = p * (dp[r][n][j] - dq_[r]);
+            if constexpr (DROP)
+              s[r][n][j] = p * __builtin_fmaf(keep8(x[n], j, drop.thr) ? drop.scale : 0.f, dp[r][n][j], -dq_[r]);
+            else
+              s[r][n][j] = p * (dp[r][n][j] - dq_[r]);
           }
         dsb[r][0] = pack8(s[r][0], s[r][1]);
         dsb[r][1] = pack8(s[r][2], s[r][3]);
@@ -947,10 +1034,14 @@ __global__ __launch_bounds__(256) void attn_dq_k(const u16* __restrict__ qkv, co
 // dK, dV: per key block of 128 (4 waves x 32 keys), sweeping the query tiles at or after it.
 // S and dP are computed with the key on the lane, so P and dS are directly the B operands of
 // dV^T += dO^T P and dK^T += Q^T dS; dO^T and Q^T come from transposing LDS reads.
+// DROP: dV = (keep * scale * P)^T dO (scale applied to the output) and dS as in attn_dq_k. Here the
+// key is on the lane: lane m = li & 3 needs byte m of all four words of every tile, so each word is
+// broadcast across the quad and the byte extracted - no transpose.
+template <bool DROP>
 __global__ __launch_bounds__(256) void attn_dkdv_k(const u16* __restrict__ qkv, const u16* __restrict__ dout,
                                                    const float* __restrict__ lse, const float* __restrict__ delta,
                                                    u16* __restrict__ dqkv, int T, int H, int BH, float c,
-                                                   float sm_scale) {
+                                                   float sm_scale, const DropSpec drop) {
   __shared__ __align__(16) u16 sm[2][2][KT * LDK];
   __shared__ __align__(16) float rowc[2][2][KT];  // [buf][lse, delta][q]
   const int bh = blockIdx.x % BH, kb = blockIdx.x / BH;  // key block 0 (most query tiles) first
@@ -981,6 +1072,9 @@ __global__ __launch_bounds__(256) void attn_dkdv_k(const u16* __restrict__ qkv, 
       dk[cc][mm] = f32x4{0.f, 0.f, 0.f, 0.f};
       dv[cc][mm] = dk[cc][mm];
     }
+
+  [[maybe_unused]] uint32_t step = 0;
+  if constexpr (DROP) step = (uint32_t)*drop.step;
 
   const int t0 = kb * QB / KT, ntiles = T / KT;
   TileLoader ld;
@@ -1038,6 +1132,13 @@ __global__ __launch_bounds__(256) void attn_dkdv_k(const u16* __restrict__ qkv, 
       }
       const bool diag = q0t < k0w + 31;
       bf16x8 pb[2][2], dsb[2][2];
+      [[maybe_unused]] u32x4 wt[2];  // this lane's tile n = li & 3: queries q0t + 16 n + 4 g + 0..3, the quad's keys
+      if constexpr (DROP) {
+#pragma unroll
+        for (int cc = 0; cc < 2; ++cc)
+          wt[cc] = attn_tile_words((uint32_t)(bh * (T >> 2) + (q0t >> 2) + 4 * (li & 3) + g), (uint32_t)(T >> 2),
+                                   (uint32_t)(((k0w + 16 * cc) >> 2) + (li >> 2)), drop, step);
+      }
 #pragma unroll
       for (int n = 0; n < 4; ++n) {
         const f32x4 lq = *reinterpret_cast<const f32x4*>(&rowc[buf][0][16 * n + 4 * g]);
@@ -1045,12 +1146,20 @@ __global__ __launch_bounds__(256) void attn_dkdv_k(const u16* __restrict__ qkv, 
 #pragma unroll
         for (int cc = 0; cc < 2; ++cc) {
           const int key = k0w + 16 * cc + li;
+          [[maybe_unused]] u32x4 x;  // x[j]: the word of query j of tile n (its byte li & 3 is this lane's key)
+          if constexpr (DROP) x = quad_bcast4(wt[cc], n);
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[cc][n][j], c, -lq[j]));
             if (diag && key > q0t + 16 * n + 4 * g + j) p = 0.f;
-            s[cc][n][j] = p;
-            dp[cc][n][j] = p * (dp[cc][n][j] - dq[j]);
+            if constexpr (DROP) {
+              const bool keep = keep8(x[j], li & 3, drop.thr);
+              s[cc][n][j] = keep ? p : 0.f;
+              dp[cc][n][j] = p * __builtin_fmaf(keep ? drop.scale : 0.f, dp[cc][n][j], -dq[j]);
+            } else {
+              s[cc][n][j] = p;
+              dp[cc][n][j] = p * (dp[cc][n][j] - dq[j]);
+            }
           }
         }
       }
@@ -1088,6 +1197,7 @@ __global__ __launch_bounds__(256) void attn_dkdv_k(const u16* __restrict__ qkv, 
       *reinterpret_cast<u32x2*>(krow + C + 16 * mm + 4 * g) =
           u32x2{pack2(dk[cc][mm][0] * sm_scale, dk[cc][mm][1] * sm_scale),
                 pack2(dk[cc][mm][2] * sm_scale, dk[cc][mm][3] * sm_scale)};
+      if constexpr (DROP) dv[cc][mm] *= drop.scale;
       *reinterpret_cast<u32x2*>(krow + 2 * C + 16 * mm + 4 * g) =
           u32x2{pack2(dv[cc][mm][0], dv[cc][mm][1]), pack2(dv[cc][mm][2], dv[cc][mm][3])};
     }
@@ -1227,27 +1337,57 @@ hipError_t colsum(const bf16* x, int M, int N, float* part, bf16* out, hipStream
   return reduce_rows(part, R, N, out, st);
 }
 
-hipError_t attn_fwd(const bf16* qkv, bf16* o, float* lse, int B, int T, int H, float sm_scale, hipStream_t st) {
+namespace {
+template <bool DROP>
+hipError_t attn_fwd_t(const bf16* qkv, bf16* o, float* lse, int B, int T, int H, float sm_scale, const DropSpec& drop,
+                      hipStream_t st) {
   const int BH = B * H;
-  hipLaunchKernelGGL(attn_fwd_k, dim3((T / QB) * BH), dim3(256), 0, st, reinterpret_cast<const u16*>(qkv),
-                     reinterpret_cast<u16*>(o), lse, T, H, BH, sm_scale * kLog2e);
+  hipLaunchKernelGGL(attn_fwd_k<DROP>, dim3((T / QB) * BH), dim3(256), 0, st, reinterpret_cast<const u16*>(qkv),
+                     reinterpret_cast<u16*>(o), lse, T, H, BH, sm_scale * kLog2e, drop);
   return hipGetLastError();
 }
 
-hipError_t attn_bwd(const bf16* qkv, const bf16* o, const bf16* dout, const float* lse, float* delta, bf16* dqkv,
-                    int B, int T, int H, float sm_scale, hipStream_t st) {
+template <bool DROP>
+hipError_t attn_bwd_t(const bf16* qkv, const bf16* o, const bf16* dout, const float* lse, float* delta, bf16* dqkv,
+                      int B, int T, int H, float sm_scale, const DropSpec& drop, hipStream_t st) {
   const int BH = B * H;
   const int64_t n = (int64_t)B * T * H;
   const u16* q = reinterpret_cast<const u16*>(qkv);
   const u16* d = reinterpret_cast<const u16*>(dout);
   u16* dq = reinterpret_cast<u16*>(dqkv);
+  // delta = sum_d dO * O needs no mask: sum_k Pd dPd = sum_k P dP with O the dropped output
   hipLaunchKernelGGL(attn_delta_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                      reinterpret_cast<const u16*>(o), d, delta, T, H, n);
-  hipLaunchKernelGGL(attn_dkdv_k, dim3((T / QB) * BH), dim3(256), 0, st, q, d, lse, delta, dq, T, H, BH,
-                     sm_scale * kLog2e, sm_scale);
-  hipLaunchKernelGGL(attn_dq_k, dim3((T / QB) * BH), dim3(256), 0, st, q, d, lse, delta, dq, T, H, BH,
-                     sm_scale * kLog2e, sm_scale);
+  hipLaunchKernelGGL(attn_dkdv_k<DROP>, dim3((T / QB) * BH), dim3(256), 0, st, q, d, lse, delta, dq, T, H, BH,
+                     sm_scale * kLog2e, sm_scale, drop);
+  hipLaunchKernelGGL(attn_dq_k<DROP>, dim3((T / QB) * BH), dim3(256), 0, st, q, d, lse, delta, dq, T, H, BH,
+                     sm_scale * kLog2e, sm_scale, drop);
   return hipGetLastError();
+}
+
+// thr holds the 8-bit threshold of the attention contract; 0 would be "keep everything" (the plain kernels)
+bool attn_drop_ok(const DropSpec& drop) { return drop.step != nullptr && drop.thr >= 1 && drop.thr <= 255; }
+}  // namespace
+
+hipError_t attn_fwd(const bf16* qkv, bf16* o, float* lse, int B, int T, int H, float sm_scale, hipStream_t st) {
+  return attn_fwd_t<false>(qkv, o, lse, B, T, H, sm_scale, DropSpec{}, st);
+}
+
+hipError_t attn_fwd(const bf16* qkv, bf16* o, float* lse, int B, int T, int H, float sm_scale, const DropSpec& drop,
+                    hipStream_t st) {
+  if (!attn_drop_ok(drop)) return hipErrorInvalidValue;
+  return attn_fwd_t<true>(qkv, o, lse, B, T, H, sm_scale, drop, st);
+}
+
+hipError_t attn_bwd(const bf16* qkv, const bf16* o, const bf16* dout, const float* lse, float* delta, bf16* dqkv,
+                    int B, int T, int H, float sm_scale, hipStream_t st) {
+  return attn_bwd_t<false>(qkv, o, dout, lse, delta, dqkv, B, T, H, sm_scale, DropSpec{}, st);
+}
+
+hipError_t attn_bwd(const bf16* qkv, const bf16* o, const bf16* dout, const float* lse, float* delta, bf16* dqkv,
+                    int B, int T, int H, float sm_scale, const DropSpec& drop, hipStream_t st) {
+  if (!attn_drop_ok(drop)) return hipErrorInvalidValue;
+  return attn_bwd_t<true>(qkv, o, dout, lse, delta, dqkv, B, T, H, sm_scale, drop, st);
 }
 
 }  // namespace tfm

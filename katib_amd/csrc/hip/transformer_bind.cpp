@@ -338,6 +338,42 @@ void attn_bwd(const Tensor& qkv, const Tensor& o, const Tensor& dout, const Tens
      "attn_bwd");
 }
 
+// the attention-probability site draws 8 bits per element (transformer.h): thr carries thr8 in 1..255,
+// scale = 256 / (256 - thr8); a p that rounds to thr8 = 0 is no dropout and belongs to attn_fwd / attn_bwd
+T_::DropSpec attn_drop_spec(double p, int64_t site, int64_t seed, const Tensor& step) {
+  T_::DropSpec dp = drop_spec(p, site, seed, step);
+  dp.thr = (uint32_t)std::floor(p * 256.0 + 0.5);
+  TORCH_CHECK(dp.thr >= 1, "attention dropout: p = ", p, " is below 1/512 (inactive); call the plain entry point");
+  dp.scale = 256.0f / (256.0f - (float)dp.thr);
+  return dp;
+}
+
+void attn_fwd_drop(const Tensor& qkv, const Tensor& o, const Tensor& lse, int64_t B, int64_t Tn, int64_t H,
+                   double sm_scale, double p, int64_t site, int64_t seed, const Tensor& step) {
+  check_attn(B, Tn, H);
+  chk(qkv, at::kBFloat16, B * Tn * 3 * H * 64, "qkv");
+  chk(o, at::kBFloat16, B * Tn * H * 64, "o");
+  chk(lse, at::kFloat, B * H * Tn, "lse");
+  ok(T_::attn_fwd(bp(qkv), bp(o), lse.data_ptr<float>(), (int)B, (int)Tn, (int)H, (float)sm_scale,
+                  attn_drop_spec(p, site, seed, step), stream()),
+     "attn_fwd_drop");
+}
+
+void attn_bwd_drop(const Tensor& qkv, const Tensor& o, const Tensor& dout, const Tensor& lse, const Tensor& delta,
+                   const Tensor& dqkv, int64_t B, int64_t Tn, int64_t H, double sm_scale, double p, int64_t site,
+                   int64_t seed, const Tensor& step) {
+  check_attn(B, Tn, H);
+  chk(qkv, at::kBFloat16, B * Tn * 3 * H * 64, "qkv");
+  chk(o, at::kBFloat16, B * Tn * H * 64, "o");
+  chk(dout, at::kBFloat16, B * Tn * H * 64, "dout");
+  chk(lse, at::kFloat, B * H * Tn, "lse");
+  chk(delta, at::kFloat, B * H * Tn, "delta");
+  chk(dqkv, at::kBFloat16, B * Tn * 3 * H * 64, "dqkv");
+  ok(T_::attn_bwd(bp(qkv), bp(o), bp(dout), lse.data_ptr<float>(), delta.data_ptr<float>(), bp(dqkv), (int)B,
+                  (int)Tn, (int)H, (float)sm_scale, attn_drop_spec(p, site, seed, step), stream()),
+     "attn_bwd_drop");
+}
+
 // C[M][N] = A[M][K] . W[N][K]^T (+ bias[N]); G given: C = pre-activation, G = gelu_tanh(C)
 void gemm_nt(const Tensor& A, const Tensor& W, const c10::optional<Tensor>& bias, const Tensor& C,
              const c10::optional<Tensor>& G) {
@@ -497,4 +533,11 @@ void register_transformer(py::module& m) {
   m.def("colsum", &colsum, "bf16 column sums of a [M, N] bf16 matrix (bias gradients)");
   m.def("attn_fwd", &attn_fwd, "causal flash attention forward, head dim 64 (MFMA)");
   m.def("attn_bwd", &attn_bwd, "causal flash attention backward (delta, dK/dV, dQ)");
+  m.def("attn_fwd_drop", &attn_fwd_drop, "attn_fwd with Philox dropout of the probabilities (8-bit draws, 4x4 tiles)",
+        py::arg("qkv"), py::arg("o"), py::arg("lse"), py::arg("B"), py::arg("T"), py::arg("H"), py::arg("sm_scale"),
+        py::arg("p"), py::arg("site"), py::arg("seed"), py::arg("step"));
+  m.def("attn_bwd_drop", &attn_bwd_drop, "attn_bwd with the mask attn_fwd_drop drew",
+        py::arg("qkv"), py::arg("o"), py::arg("dout"), py::arg("lse"), py::arg("delta"), py::arg("dqkv"), py::arg("B"),
+        py::arg("T"), py::arg("H"), py::arg("sm_scale"), py::arg("p"), py::arg("site"), py::arg("seed"),
+        py::arg("step"));
 }

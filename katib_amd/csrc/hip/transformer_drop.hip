@@ -25,6 +25,7 @@
 //  * dropout_f32_k   in place over an fp32 [M, D] tensor (the embedding sum and its gradient).
 //  * dropout_mask_k  the keep mask itself as bytes (tests only), from the same device function.
 #include "transformer.h"
+#include "philox.h"
 
 namespace katib_hip {
 namespace tfm {
@@ -46,19 +47,7 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11).
-__device__ __forceinline__ u32x4 philox4x32_10(u32x4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-    c = u32x4{(uint32_t)(p1 >> 32) ^ c[1] ^ k0, (uint32_t)p1, (uint32_t)(p0 >> 32) ^ c[3] ^ k1, (uint32_t)p0};
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c;
-}
-
+// (philox4x32_10: philox.h, shared with the attention kernels of transformer.hip)
 // The four random words of elements e .. e + 3 (e % 4 == 0) of a dropout site at this step.
 __device__ __forceinline__ u32x4 drop_words(int64_t e, const DropSpec& dp, uint32_t step) {
   const uint64_t q = (uint64_t)e >> 2;

@@ -38,7 +38,7 @@ import torch.nn.functional as F
 # attn-proj / fc2 bias gradients summed by the LayerNorm backward that writes their output gradient
 _LN_BIAS = True  # (module attribute; False: a separate column-sum pass per bias, as before)
 
-from ..ops.transformer import Drop, check_dropout_p
+from ..ops.transformer import Drop, attn_dropout_threshold, check_dropout_p
 from ..utils.tracing import gpu_range
 
 
@@ -70,6 +70,10 @@ class GPT2Flat:
         self.dtype = dtype
         # residual / embedding dropout, training only; the mask stream is keyed by (site, seed, step_t)
         self.dropout = check_dropout_p(getattr(cfg, "dropout", 0.0))
+        # attention-probability dropout, an independent switch: 8-bit draws inside the flash attention
+        # kernels (ops/transformer.py attn_dropout_mask), so a value below 1/512 is no dropout at all
+        self.attn_dropout = check_dropout_p(getattr(cfg, "attn_dropout", 0.0))
+        self._attn_on = attn_dropout_threshold(self.attn_dropout) > 0
         self.seed = int(seed)
         self.V = cfg.vocab
         self.Vp = (cfg.vocab + 63) // 64 * 64
@@ -165,10 +169,19 @@ class GPT2Flat:
         the same mask, and a resumed checkpoint continues the stream."""
         return Drop(self.dropout, site, self.seed, self.step_t) if (train and self.dropout > 0.0) else None
 
+    def _attn_kw(self, i: int, train: bool):
+        """Keyword arguments of block ``i``'s two attention calls: its attention-probability dropout
+        site (id 2 n_layer + 1 + i) in a training pass, nothing otherwise (the calls made before this
+        site existed)."""
+        if not (train and self._attn_on):
+            return {}
+        return {"drop": Drop(self.attn_dropout, 2 * self.cfg.n_layer + 1 + i, self.seed, self.step_t)}
+
     def forward(self, idx, save: bool = False, train: bool = False):
         """Logits [B*T, Vp] (pad columns are zero-weight rows; ignore them). ``train``: apply
         ``cfg.dropout`` to the embedding sum and to every proj / fc2 output (inside the residual-add
-        LayerNorm that consumes it). Attention-probability dropout is not implemented."""
+        LayerNorm that consumes it), and ``cfg.attn_dropout`` to the attention probabilities (inside
+        the flash attention kernels)."""
         c, ops = self.cfg, self.ops
         B, T = idx.shape
         H = c.n_head
@@ -180,7 +193,7 @@ class GPT2Flat:
             sa, h1, mu1, rs1 = ops.ln_fwd(resid, pending, self.w[pre + "ln1.weight"], self.w[pre + "ln1.bias"],
                                           drop=self._drop(2 * i - 1, train and i > 0))  # the lower block's fc2
             qkv = self._lin(h1, pre + "qkv")
-            o, lse = ops.attn_fwd(qkv, B, T, H, c.d // H)
+            o, lse = ops.attn_fwd(qkv, B, T, H, c.d // H, **self._attn_kw(i, train))
             a = self._lin(o, pre + "proj")
             sb, h2, mu2, rs2 = ops.ln_fwd(sa, a, self.w[pre + "ln2.weight"], self.w[pre + "ln2.bias"],
                                           drop=self._drop(2 * i, train))
@@ -257,7 +270,7 @@ class GPT2Flat:
             if not lb:
                 ops.colsum(dr, g[pre + "proj.bias"])
             do = ops.dgrad(dr, self.w[pre + "proj.weight"])
-            dqkv = ops.attn_bwd(qkv, o, do, lse, B, T, H, d // H)
+            dqkv = ops.attn_bwd(qkv, o, do, lse, B, T, H, d // H, **self._attn_kw(i, train))
             ops.wgrad_bgrad(dqkv, h1, g[pre + "qkv.weight"], g[pre + "qkv.bias"])
             dh1 = ops.dgrad(dqkv, self.w[pre + "qkv.weight"])
             del dqkv

@@ -24,6 +24,10 @@ Contracts (``M`` rows, ``D`` features, ``Vp`` padded vocabulary of which ``V`` a
     causal softmax attention with head dim 64; ``qkv`` is ``[B*T, 3*H*64]`` (q | k | v, heads
     contiguous), ``o`` is ``[B*T, H*64]``, ``lse`` ``[B, H, T]`` = log2-sum-exp2 of the
     scaled scores (in log2 units).
+``attn_fwd(..., drop=Drop(...))`` / ``attn_bwd(..., drop=...)``
+    dropout of the attention probabilities: ``o = (keep * scale * softmax(s)) @ v`` with the 8-bit
+    mask contract above :func:`attn_dropout_mask`; ``lse`` stays that of the undropped softmax.
+    ``drop=None`` or a ``p`` below 1/512: the calls above, unchanged.
 ``xent_fwd(logits, tgt, V) -> (loss_rows, lse)``; ``xent_bwd(logits, tgt, lse, gscale, V)``
     writes ``(softmax - onehot) * gscale / N`` over ``logits`` in place.
 """
@@ -142,6 +146,50 @@ def _active(drop) -> bool:
     return drop is not None and check_dropout_p(drop.p) > 0.0
 
 
+# ---------------------------------------------------------------- attention-probability dropout
+# The third dropout site of a GPT-2 block acts on the probabilities P [B*H, T, T] inside the flash
+# attention kernels, which never store P. A 32-bit word per probability (the contract above) would
+# cost one Philox call per 4 probabilities, several times the softmax's own arithmetic, so this site
+# draws 8 bits per element on 4 x 4 tiles - one call serves 16 probabilities:
+#   bh = b * H + h, query q, key k, T % 4 == 0;
+#   blk = (bh * (T / 4) + (q >> 2)) * (T / 4) + (k >> 2) (64-bit);
+#   w = Philox4x32-10(counter = (blk & 0xffffffff, blk >> 32, site, step), key as above);
+#   byte = (w[q & 3] >> (8 * (k & 3))) & 0xff; the element is kept iff byte >= thr8 = floor(p * 256 + 0.5);
+#   kept values are multiplied by scale = 256 / (256 - thr8), computed in fp32.
+# The realised drop probability is thr8 / 256 (a 1/256 grid; the scale is unbiased for that, not for
+# the p asked for), and a p below 1/512 rounds to thr8 = 0: the site is inactive and takes the p = 0
+# path. The causal mask is applied separately; the draw of a masked position is never used.
+def attn_dropout_threshold(p: float) -> int:
+    return int(math.floor(check_dropout_p(p) * 256.0 + 0.5))
+
+
+def attn_dropout_scale(p: float) -> float:
+    t = torch.tensor(256.0, dtype=torch.float32)
+    return float(t / (t - torch.tensor(float(attn_dropout_threshold(p)), dtype=torch.float32)))
+
+
+def attn_dropout_mask(B: int, H: int, T: int, p: float, site: int, seed: int, step, device=None):
+    """Keep mask (bool [B, H, T, T], causality not applied) of one attention dropout site at one
+    step; ``step`` is an int or the device step tensor (read as uint32, no host sync)."""
+    if T % 4:
+        raise ValueError("attn_dropout_mask: T must be a multiple of 4")
+    thr8 = attn_dropout_threshold(p)
+    if torch.is_tensor(step):
+        device = step.device if device is None else device
+        step = step.reshape(()).to(device=device, dtype=torch.int64)
+    T4 = T // 4
+    blk = torch.arange(B * H * T4 * T4, dtype=torch.int64, device=device)  # (bh, q >> 2, k >> 2) row-major
+    words = philox4x32((blk & _M32, blk >> 32, int(site), step), (int(seed) & _M32, (int(seed) >> 32) & _M32))
+    w = torch.stack(words, -1).view(B * H, T4, T4, 4, 1)  # [bh, q >> 2, k >> 2, q & 3, .]
+    shifts = torch.arange(0, 32, 8, dtype=torch.int64, device=device)  # 8 * (k & 3)
+    keep = ((w >> shifts) & 0xFF) >= thr8  # [bh, q >> 2, k >> 2, q & 3, k & 3]
+    return keep.permute(0, 1, 3, 2, 4).reshape(B, H, T, T)
+
+
+def _attn_active(drop) -> bool:
+    return drop is not None and attn_dropout_threshold(drop.p) > 0
+
+
 class TorchOps:
     name = "torch"
 
@@ -213,22 +261,32 @@ class TorchOps:
         return (dy.float() * d).to(u.dtype)
 
     # ---------------------------------------------------------------- attention
-    def attn_fwd(self, qkv, B, T, H, hd=64):
+    def _attn_dropped(self, p, B, T, H, drop):
+        """``keep * scale * p`` for the probabilities p [B, H, T, T] (fp32)."""
+        keep = attn_dropout_mask(B, H, T, drop.p, drop.site, drop.seed, drop.step, p.device)
+        return torch.where(keep, p * attn_dropout_scale(drop.p), torch.zeros_like(p))
+
+    def attn_fwd(self, qkv, B, T, H, hd=64, drop=None):
         q, k, v = qkv.float().view(B, T, 3, H, hd).permute(2, 0, 3, 1, 4)
         s = (q @ k.transpose(-1, -2)) / math.sqrt(hd)
         mask = torch.ones(T, T, dtype=torch.bool, device=qkv.device).triu(1)
         s = s.masked_fill(mask, float("-inf"))
         lse = torch.logsumexp(s, -1)
-        o = torch.softmax(s, -1) @ v
+        p = torch.softmax(s, -1)
+        if _attn_active(drop):
+            p = self._attn_dropped(p, B, T, H, drop)
+        o = p @ v
         return o.permute(0, 2, 1, 3).reshape(B * T, H * hd).to(qkv.dtype), lse * LOG2E
 
-    def attn_bwd(self, qkv, o, dout, lse, B, T, H, hd=64):
+    def attn_bwd(self, qkv, o, dout, lse, B, T, H, hd=64, drop=None):
         with torch.enable_grad():
             x = qkv.detach().float().requires_grad_(True)
             q, k, v = x.view(B, T, 3, H, hd).permute(2, 0, 3, 1, 4)
             s = (q @ k.transpose(-1, -2)) / math.sqrt(hd)
             mask = torch.ones(T, T, dtype=torch.bool, device=qkv.device).triu(1)
             p = torch.softmax(s.masked_fill(mask, float("-inf")), -1)
+            if _attn_active(drop):
+                p = self._attn_dropped(p, B, T, H, drop)
             out = (p @ v).permute(0, 2, 1, 3).reshape(B * T, H * hd)
             (g,) = torch.autograd.grad(out, x, dout.float())
         return g.to(qkv.dtype)
@@ -431,16 +489,26 @@ class HipOps:
         self.wgrad(dy, x, dw)
         self.colsum(dy, db)
 
-    def attn_fwd(self, qkv, B, T, H, hd=64):
+    def attn_fwd(self, qkv, B, T, H, hd=64, drop=None):
+        """``drop``: dropout of the attention probabilities, the mask recomputed inside the flash
+        kernels (attn_fwd_k<true>; contract above :func:`attn_dropout_mask`)."""
         assert hd == 64
         o = torch.empty((B * T, H * hd), device=qkv.device, dtype=torch.bfloat16)
         lse = torch.empty((B, H, T), device=qkv.device, dtype=torch.float32)
+        if _attn_active(drop):
+            self.k.attn_fwd_drop(qkv, o, lse, B, T, H, 1.0 / math.sqrt(hd), drop.p, drop.site, drop.seed,
+                                 drop.step)
+            return o, lse
         self.k.attn_fwd(qkv, o, lse, B, T, H, 1.0 / math.sqrt(hd))
         return o, lse
 
-    def attn_bwd(self, qkv, o, dout, lse, B, T, H, hd=64):
+    def attn_bwd(self, qkv, o, dout, lse, B, T, H, hd=64, drop=None):
         dqkv = torch.empty_like(qkv)
         delta = torch.empty_like(lse)
+        if _attn_active(drop):
+            self.k.attn_bwd_drop(qkv, o, dout, lse, delta, dqkv, B, T, H, 1.0 / math.sqrt(hd), drop.p, drop.site,
+                                 drop.seed, drop.step)
+            return dqkv
         self.k.attn_bwd(qkv, o, dout, lse, delta, dqkv, B, T, H, 1.0 / math.sqrt(hd))
         return dqkv
 

@@ -17,11 +17,15 @@ path (the CPU default and the numerical oracle). Data: synthetic Markov-chain to
 resident in HBM.
 
 ``--dropout p`` (0 <= p <= 0.9, a PBT-tunable hyperparameter, ``examples/pbt/pbt-gpt2-small-dropout.yaml``)
-drops the embedding sum and every attention-proj / MLP-fc2 output while training; evaluation never
-drops and attention-probability dropout is fixed at 0. The flat model's masks come from a
+drops the embedding sum and every attention-proj / MLP-fc2 output while training; ``--attn-dropout p``
+(same range, an independent switch, ``examples/pbt/pbt-gpt2-small-attn-dropout.yaml``) drops the
+attention probabilities; evaluation never drops. The flat model's masks come from a
 counter-based generator keyed by ``--seed`` and the checkpointed step counter (fused into the
-LayerNorm kernels, ``csrc/hip/transformer_drop.hip``), so a child that resumes a parent continues
-its mask stream; the ``nn.Module`` path uses ``F.dropout`` (statistically, not bitwise, the same).
+LayerNorm kernels, ``csrc/hip/transformer_drop.hip``, and recomputed inside the flash attention
+kernels, ``csrc/hip/transformer.hip``), so a child that resumes a parent continues its mask stream;
+the ``nn.Module`` path uses ``F.dropout`` and SDPA's ``dropout_p`` (statistically, not bitwise, the
+same). The attention site draws 8 bits per probability: its realised rate is ``round(256 p) / 256``
+and a ``p`` below 1/512 is no dropout.
 
 Checkpoints: the parent's state is fetched GPU-to-GPU from the warm worker that
 trained it (:mod:`katib_amd.parallel.p2p_ckpt`, peer copy over xGMI); ``model.pt`` +
@@ -59,6 +63,7 @@ class GPTConfig:
     n_head: int = 12
     d: int = 768
     dropout: float = 0.0
+    attn_dropout: float = 0.0
 
 
 PRESETS = {
@@ -87,6 +92,7 @@ class Block(nn.Module):
         self.fc2 = nn.Linear(4 * c.d, c.d)
         self.h = c.n_head
         self.p = c.dropout  # residual dropout on the proj / fc2 outputs (a float: state_dict keys unchanged)
+        self.attn_p = c.attn_dropout  # attention-probability dropout (SDPA's dropout_p), likewise a float
 
     def _drop(self, t):
         return F.dropout(t, self.p, self.training) if self.p > 0 else t
@@ -97,7 +103,10 @@ class Block(nn.Module):
         q = q.view(B, T, self.h, D // self.h).transpose(1, 2)
         k = k.view(B, T, self.h, D // self.h).transpose(1, 2)
         v = v.view(B, T, self.h, D // self.h).transpose(1, 2)
-        a = F.scaled_dot_product_attention(q, k, v, is_causal=True)
+        if self.attn_p > 0 and self.training:  # framework RNG, as _drop: the statistical reference
+            a = F.scaled_dot_product_attention(q, k, v, dropout_p=self.attn_p, is_causal=True)
+        else:
+            a = F.scaled_dot_product_attention(q, k, v, is_causal=True)
         x = x + self._drop(self.proj(a.transpose(1, 2).reshape(B, T, D)))
         return x + self._drop(self.fc2(F.gelu(self.fc(self.ln2(x)), approximate="tanh")))
 
@@ -157,10 +166,15 @@ def parse_args(argv):
     p.add_argument("--ops", default="auto", choices=["auto", "hip", "torch"], help="kernel backend of --impl flat")
     p.add_argument("--dropout", type=float, default=0.0,
                    help="dropout on the embedding sum and the proj / fc2 outputs, 0 <= p <= %g "
-                        "(attention-probability dropout is fixed at 0)" % DROPOUT_MAX_P)
+                        "(attention-probability dropout: --attn-dropout)" % DROPOUT_MAX_P)
+    p.add_argument("--attn-dropout", type=float, default=0.0,
+                   help="dropout on the attention probabilities, 0 <= p <= %g, independent of --dropout "
+                        "(--impl flat: realised in steps of 1/256)" % DROPOUT_MAX_P)
     args = p.parse_args(argv)
     if not 0.0 <= args.dropout <= DROPOUT_MAX_P:
         p.error("--dropout must be in [0, %g], got %r" % (DROPOUT_MAX_P, args.dropout))
+    if not 0.0 <= args.attn_dropout <= DROPOUT_MAX_P:
+        p.error("--attn-dropout must be in [0, %g], got %r" % (DROPOUT_MAX_P, args.attn_dropout))
     return args
 
 
@@ -199,7 +213,7 @@ def main(argv=None):
     dev = device()
     cuda = dev.type == "cuda"
     torch.manual_seed(args.seed)
-    cfg = dataclasses.replace(PRESETS[args.model], dropout=args.dropout)
+    cfg = dataclasses.replace(PRESETS[args.model], dropout=args.dropout, attn_dropout=args.attn_dropout)
     T = args.seq_len or cfg.ctx
     toks = markov_tokens(args.num_tokens, vocab=cfg.vocab, seed=99, dev=dev)
     n_train = int(len(toks) * 0.9)
