@@ -32,6 +32,7 @@ import torch
 import torch.nn as nn
 
 from .. import _hipload
+from .augment import augment_gather
 
 
 def kernels():
@@ -115,18 +116,35 @@ class FusedResNetStep:
 
     ``tx`` [N, 3, H, W] bf16 channels_last and ``ty`` [N] int64 are the device-resident data
     set, ``idx`` [B] int64 the batch indices the caller refreshes before each call,
-    ``loss_buf`` a float32 scalar the step adds the batch loss to."""
+    ``loss_buf`` a float32 scalar the step adds the batch loss to.
 
-    def __init__(self, model, tx, ty, idx, loss_buf, lr, momentum, weight_decay, nesterov=True):
+    ``aug`` (an ``ops.augment.AugSpec``, its ``epoch`` usually a one-element int32 device tensor
+    the caller fills once per epoch, outside the graph) replaces the first launch, ``rn_gather``,
+    by ``augment_gather`` into the same ``x0``: random crop + flip keyed by data-set index. ``src``
+    = ``(packed [N, H, W, 4] uint8, lut [3, 256])`` reads a raw-byte data set instead of ``tx``
+    (which may then be ``None``); it needs ``aug`` (``ops.augment.PLAIN`` for no augmentation).
+    Without ``aug`` the step makes exactly the launches it made before."""
+
+    def __init__(self, model, tx, ty, idx, loss_buf, lr, momentum, weight_decay, nesterov=True, aug=None, src=None):
         self.k = k = kernels()
-        dev = tx.device
+        dev = idx.device
         self.model, self.ty, self.idx, self.loss_buf = model, ty, idx, loss_buf
         self.lr, self.mom, self.wd, self.nesterov = float(lr), float(momentum), float(weight_decay), bool(nesterov)
-        self.txn = tx.permute(0, 2, 3, 1)
-        if not self.txn.is_contiguous() or tx.dtype != torch.bfloat16:
-            raise ValueError("fused ResNet step: images must be bf16 channels_last")
+        self.aug, self.aug_lut = aug, None
+        if src is not None:
+            if aug is None:
+                raise ValueError("fused ResNet step: a u8 source is read by augment_gather and needs aug "
+                                 "(ops.augment.PLAIN for a plain normalising gather)")
+            self.txn, self.aug_lut = src
+            if self.txn.dtype != torch.uint8 or self.txn.dim() != 4 or self.txn.shape[3] != 4:
+                raise ValueError("fused ResNet step: src must be (packed [N, H, W, 4] uint8, lut [C, 256])")
+            _, H, W, _ = self.txn.shape
+        else:
+            self.txn = tx.permute(0, 2, 3, 1)
+            if not self.txn.is_contiguous() or tx.dtype != torch.bfloat16:
+                raise ValueError("fused ResNet step: images must be bf16 channels_last")
+            _, _, H, W = tx.shape
         B = idx.numel()
-        _, _, H, W = tx.shape
         stem = _Conv(model.stem_conv, B, H, W, dgrad=False, dev=dev)
         self.x0 = torch.empty(B, H, W, stem.C8, device=dev, dtype=torch.bfloat16)
         self.stem, self.stem_bn = stem, _BN(model.stem_bn, stem, True, dev)
@@ -185,7 +203,10 @@ class FusedResNetStep:
         k = self.k
         stem, sbn = self.stem, self.stem_bn
         # ---- forward
-        k.rn_gather(self.txn, self.idx, self.x0)
+        if self.aug is None:
+            k.rn_gather(self.txn, self.idx, self.x0)
+        else:
+            augment_gather(self.txn, self.idx, self.aug, self.aug_lut, c8=self.x0.shape[3], out=self.x0)
         k.conv_fwd(self.x0, stem.wk, stem.y, stem.geom)
         sbn.fwd(k)
         a = sbn.y

@@ -15,6 +15,18 @@ data. BN batch statistics are per rank (DDP semantics, no SyncBN); the running s
 used by validation are averaged over the ranks before every validation pass, and the
 validation accuracy is the global one, ``sum(correct) / sum(n)`` over all ranks' shards
 (the reference averages over the whole valid split, ``run_trial.py:225-255``).
+
+Data and augmentation. ``--data-dir DIR`` trains on the CIFAR-10 binary version found there
+(``workloads/data.py: cifar10_from_dir``; ``--num-train`` caps the 50,000 images before the 50/50
+split) instead of the synthetic set. ``--augment {auto,0,1}`` turns on the reference's
+``train_transform`` - ``RandomCrop(32, padding=4)`` + ``RandomHorizontalFlip`` ahead of the
+normalisation - fused into the on-device batch gather (``ops/augment.py``); ``auto`` is on with
+``--data-dir`` and off on synthetic data. The reference builds its weight loader, its architect
+loader AND its per-epoch validation loader from the one augmented ``train_data``
+(``run_trial.py``: all three share ``train_transform``), so all three passes are augmented here
+too, each with its own draw stream: 0 the weight batches, 1 the architect's batches, 2 the
+validation pass; seed 2 (the reference's fixed seed), ``epoch`` the epoch number. A draw is keyed
+by the image's data-set index, so an N-rank search sees exactly the crops of the 1-rank search.
 """
 
 from __future__ import annotations
@@ -36,6 +48,10 @@ def parse_args(argv):
     p.add_argument("--capture", type=int, default=1)
     p.add_argument("--ops", type=str, default=os.environ.get("KATIB_AMD_DARTS_OPS", "hip"))
     p.add_argument("--max-steps", type=int, default=0, help="stop each epoch after N steps (0 = full epoch)")
+    p.add_argument("--data-dir", type=str, default="",
+                   help="directory with the CIFAR-10 binary version (empty: synthetic data)")
+    p.add_argument("--augment", type=str, default="auto", choices=["auto", "0", "1"],
+                   help="random crop (pad 4) + horizontal flip in the batch gather; auto = on with --data-dir")
     return p.parse_args(argv)
 
 
@@ -82,7 +98,8 @@ def main(argv=None):
     from ..models.darts_search import DartsSearch
     from ..ops import darts as dops
     from ..parallel.comm import Comm
-    from .data import cifar10
+    from ..ops.augment import AugSpec
+    from .data import cifar10, cifar10_from_dir
 
     args = parse_args(sys.argv[1:] if argv is None else argv)
     settings = json.loads(_strip(args.algorithm_settings).replace("'", '"')) if args.algorithm_settings else {}
@@ -102,9 +119,20 @@ def main(argv=None):
     layout = DartsLayout(prims, init_channels=int(st["init_channels"]), num_layers=num_layers,
                          num_nodes=int(st["num_nodes"]), stem_multiplier=int(st["stem_multiplier"]))
     search = DartsSearch(layout, dev, comm, settings=st, capture=bool(args.capture) and dev.type == "cuda")
-    ds = cifar10(dev, n=args.num_train)
-    split = args.num_train // 2
-    train, valid = ds.subset(0, split), ds.subset(split, args.num_train)
+    if args.data_dir:
+        ds = cifar10_from_dir(args.data_dir, dev, "train", limit=args.num_train)
+        num_train = ds.n
+    else:
+        ds = cifar10(dev, n=args.num_train)
+        num_train = args.num_train
+    augment = bool(args.data_dir) if args.augment == "auto" else args.augment == "1"
+    aug = AugSpec(pad=4, flip=True, seed=2) if augment else None
+
+    def aug_of(stream, epoch):
+        return None if aug is None else aug.replace(stream=stream, epoch=epoch)
+
+    split = num_train // 2
+    train, valid = ds.subset(0, split), ds.subset(split, num_train)
     gbs = int(st["batch_size"])  # global batch
     bs = max(1, gbs // comm.world_size)  # per-rank share
     if comm.rank == 0 and bs * comm.world_size != gbs:
@@ -121,8 +149,10 @@ def main(argv=None):
     for epoch in range(epochs):
         lr = lr_min + (lr_max - lr_min) * (1 + math.cos(math.pi * epoch / epochs)) / 2
         search.set_lr(lr)
-        tb = train.batches(bs, seed=epoch, shard=comm.rank, num_shards=comm.world_size, drop_last=True)
-        vb = valid.batches(bs, seed=1000 + epoch, shard=comm.rank, num_shards=comm.world_size, drop_last=True)
+        tb = train.batches(bs, seed=epoch, shard=comm.rank, num_shards=comm.world_size, drop_last=True,
+                           augment=aug_of(0, epoch))
+        vb = valid.batches(bs, seed=1000 + epoch, shard=comm.rank, num_shards=comm.world_size, drop_last=True,
+                           augment=aug_of(1, epoch))
         nsteps = train.steps_per_epoch(bs, comm.world_size)
         for step, ((tx, ty), (vx, vy)) in enumerate(zip(tb, vb)):
             if args.max_steps and step >= args.max_steps:
@@ -135,7 +165,7 @@ def main(argv=None):
         # validation (no_grad forward over the valid split): loss / correct counts accumulate on
         # the device (no host sync per batch), then one all-reduce gives the global accuracy
         vbatches = valid.batches(bs, seed=5000 + epoch, shard=comm.rank, num_shards=comm.world_size,
-                                 drop_last=True)
+                                 drop_last=True, augment=aug_of(2, epoch))
         _, top1 = validate(search, comm, vbatches, args.max_steps)
         geno = search.genotype()
         if comm.rank == 0:

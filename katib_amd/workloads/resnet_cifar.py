@@ -10,6 +10,13 @@ device-resident synthetic data, and the
 whole train step (forward, loss, backward, SGD+Nesterov momentum) captured as one
 HIP graph.
 
+``--augment 1`` adds the standard CIFAR recipe's random crop (pad 4) + horizontal flip to the
+training batches, fused into the step's first launch (``ops/augment.py``: the draw is keyed by
+data-set index, training uses stream 0 and the epoch number; validation is never augmented).
+``--data-dir DIR`` trains on the CIFAR-10 binary version found there (train split capped by
+``--num-train``, ``test_batch.bin`` capped by ``--num-valid``), kept as raw bytes in HBM and
+normalised by the same gather.
+
 Per epoch it prints ``epoch=<e> loss=<l> Validation-accuracy=<a>``; the median-stop
 rule compares the objective after ``start_step`` reports.
 """
@@ -24,6 +31,7 @@ import torch.nn.functional as F
 
 from ..ops import batchnorm as hbn
 from ..ops import conv as hconv
+from ..ops.augment import PLAIN, AugSpec, augment_gather, augment_reference
 from .common import CapturedStep, Timer, device, global_avg_pool, pattern_images, report
 
 Conv = hconv.Conv2d  # HIP implicit GEMM on GPU, stock nn.Conv2d on CPU
@@ -59,6 +67,10 @@ def parse_args(argv):
                    help="GPU train step: 'fused' = ops/resnet_step.py (every launch a katib_hip kernel: no "
                         "autograd tape, one multi-tensor SGD launch); 'module' = the nn.Module + autograd + "
                         "torch.optim path (also used with --conv/--bn torch and on CPU)")
+    p.add_argument("--augment", type=int, default=0, choices=[0, 1],
+                   help="random crop (pad 4) + horizontal flip of the training batches, in the gather")
+    p.add_argument("--data-dir", type=str, default="",
+                   help="directory with the CIFAR-10 binary version (empty: synthetic pattern images)")
     return p.parse_args(argv)
 
 
@@ -106,10 +118,24 @@ def main(argv=None):
     torch.manual_seed(args.seed)
     cuda = dev.type == "cuda"
     mf = torch.channels_last if cuda else torch.contiguous_format
-    x, y = pattern_images(args.num_train + args.num_valid, seed=4321, dev=dev,
-                          dtype=torch.bfloat16 if cuda else torch.float32)
-    x = x.contiguous(memory_format=mf)
-    tx, ty, vx, vy = x[:args.num_train], y[:args.num_train], x[args.num_train:], y[args.num_train:]
+    act = torch.bfloat16 if cuda else torch.float32
+    tds = vds = None
+    if args.data_dir:
+        from .data import cifar10_from_dir
+
+        tds = cifar10_from_dir(args.data_dir, dev, "train", limit=args.num_train)
+        vds = cifar10_from_dir(args.data_dir, dev, "test", limit=args.num_valid)
+        args.num_train, args.num_valid = tds.n, vds.n
+        tx, ty, vx, vy = None, tds.y, None, vds.y
+    else:
+        x, y = pattern_images(args.num_train + args.num_valid, seed=4321, dev=dev, dtype=act)
+        x = x.contiguous(memory_format=mf)
+        tx, ty, vx, vy = x[:args.num_train], y[:args.num_train], x[args.num_train:], y[args.num_train:]
+    aug = epoch_t = None
+    if args.augment:
+        # the device epoch of the augmentation draws: filled once per epoch, outside the captured step
+        epoch_t = torch.zeros(1, dtype=torch.int32, device=dev)
+        aug = AugSpec(pad=4, flip=True, seed=args.seed, stream=0, epoch=epoch_t)
     model = ResNet18(args.width).to(dev).to(memory_format=mf)
     opt = torch.optim.SGD(model.parameters(), lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay,
                           nesterov=True)
@@ -120,8 +146,19 @@ def main(argv=None):
     idx = torch.zeros(bs, dtype=torch.long, device=dev)
     loss_buf = torch.zeros((), device=dev)
 
+    def drawn_batch():
+        """The (augmented and / or table-normalised) batch at ``idx`` through the torch oracle."""
+        if tds is not None:
+            xb = augment_reference(tds.x, idx, aug or PLAIN, tds.lut)
+        else:  # bf16 channels_last storage is the oracle's [N, H, W, C] bf16 form
+            xb = augment_reference(tx.permute(0, 2, 3, 1) if cuda else tx, idx, aug)
+        return xb.to(act).contiguous(memory_format=mf)
+
     def train_step():
-        xb = tx.index_select(0, idx).contiguous(memory_format=mf)
+        if aug is None and tds is None:
+            xb = tx.index_select(0, idx).contiguous(memory_format=mf)
+        else:
+            xb = drawn_batch()
         yb = ty.index_select(0, idx)
         with torch.autocast(device_type=dev.type, dtype=torch.bfloat16, enabled=cuda):
             loss = F.cross_entropy(model(xb.float() if not cuda else xb), yb)
@@ -137,7 +174,9 @@ def main(argv=None):
         from ..ops.resnet_step import FusedResNetStep
 
         model.train()
-        fused = FusedResNetStep(model, tx, ty, idx, loss_buf, args.lr, args.momentum, args.weight_decay, nesterov=True)
+        fused = FusedResNetStep(model, tx, ty, idx, loss_buf, args.lr, args.momentum, args.weight_decay, nesterov=True,
+                                aug=(aug or PLAIN) if tds is not None else aug,
+                                src=(tds.x, tds.lut) if tds is not None else None)
         train_step = fused.step  # noqa: F811 - same contract: static idx in, loss_buf out
     step = CapturedStep(train_step, enabled=bool(args.capture))
     gen = torch.Generator(device=dev).manual_seed(args.seed)
@@ -147,6 +186,8 @@ def main(argv=None):
         model.train()
         perm = torch.randperm(args.num_train, device=dev, generator=gen)[:steps * bs].view(steps, bs)
         loss_buf.zero_()
+        if epoch_t is not None:
+            epoch_t.fill_(epoch)
         for s in range(steps):
             idx.copy_(perm[s])
             step()
@@ -154,7 +195,12 @@ def main(argv=None):
         correct = torch.zeros((), device=dev)
         with torch.no_grad(), torch.autocast(device_type=dev.type, dtype=torch.bfloat16, enabled=cuda):
             for i in range(0, args.num_valid, 1024):
-                correct += (model(vx[i:i + 1024]).argmax(1) == vy[i:i + 1024]).sum()
+                if vds is None:
+                    xv = vx[i:i + 1024]
+                else:  # raw bytes: the pad-0 (normalising) gather, never augmented
+                    vi = torch.arange(i, min(i + 1024, args.num_valid), device=dev)
+                    xv = augment_gather(vds.x, vi, PLAIN, vds.lut).to(act).contiguous(memory_format=mf)
+                correct += (model(xv).argmax(1) == vy[i:i + 1024]).sum()
         acc = float(correct) / max(args.num_valid, 1)
         report(epoch=epoch, loss=float(loss_buf) / max(steps, 1), **{"Validation-accuracy": acc})
     report(train_seconds=timer.elapsed())
