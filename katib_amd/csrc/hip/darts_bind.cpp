@@ -190,25 +190,31 @@ static bool fill_dwpw(const py::tuple& t, DwPwFwdArgs& a, int64_t K, int64_t dil
                       bool use_mfma) {
   Tensor x = t[0].cast<Tensor>(), dw = t[1].cast<Tensor>(), pw = t[2].cast<Tensor>();
   auto inbn = t[3].cast<c10::optional<py::tuple>>();
-  Tensor d = t[4].cast<Tensor>(), z = t[5].cast<Tensor>();
+  OptT d = t[4].cast<OptT>();
+  Tensor z = t[5].cast<Tensor>();
   OptT stats = t[6].cast<OptT>();
+  const bool has_d = d.has_value() && d->defined();
   const bool has_inbn = t[3].cast<c10::optional<py::tuple>>().has_value();
   if (has_inbn) check_z(x, "x (previous stage z)");
   else check_f32(x, "x");
-  check_f32(dw, "dw"); check_f32(pw, "pw"); check_z(d, "d"); check_z(z, "z");
+  check_f32(dw, "dw"); check_f32(pw, "pw"); check_z(z, "z");
+  if (has_d) check_z(*d, "d");
   TORCH_CHECK(x.dim() == 4, "x must be NCHW");
   TORCH_CHECK((K == 3 || K == 5) && (dil == 1 || dil == 2) && (S == 1 || S == 2), "K in {3,5}, dil, S in {1,2}");
   const int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   const int Ho = z.size(2), Wo = z.size(3);
   TORCH_CHECK(dw.numel() == C * K * K && pw.numel() == C * C, "weight shapes");
-  TORCH_CHECK(z.size(0) == N && z.size(1) == C && d.sizes() == z.sizes(), "output shapes");
+  TORCH_CHECK(z.size(0) == N && z.size(1) == C && (!has_d || d->sizes() == z.sizes()), "output shapes");
+  // d: None only where the fused kernels run (its one reader is the pointwise weight gradient);
+  // the split path's pointwise GEMM reads it
+  TORCH_CHECK(has_d || !dwpw_split_path(C), "dw-pw stages of 16..64 channels (depthwise + pointwise GEMM) need d");
   // (C = 4 / 8 / 16 always run the row-band plane kernels, which take any width)
   TORCH_CHECK(C == 4 || C == 8 || C == 16 || (64 % Wo == 0 && Ho % (64 / Wo) == 0),
               "tile constraint: 64 % Wo == 0 and Ho % (64/Wo) == 0");
   TORCH_CHECK(C <= kMaxC, "C too large");
   TORCH_CHECK(Ho == (H + 2 * pad - dil * (K - 1) - 1) / S + 1, "output height mismatch");
   a.x = x.data_ptr(); a.dw = dw.data_ptr<float>(); a.pw = pw.data_ptr<float>();
-  a.d = zptr(d); a.z = zptr(z); a.stats = ptr_or_null<double>(stats);
+  a.d = has_d ? zptr(*d) : nullptr; a.z = zptr(z); a.stats = ptr_or_null<double>(stats);
   if (a.stats) TORCH_CHECK(stats->scalar_type() == at::kDouble && stats->numel() >= kRep * 2 * C, "stats f64 [kRep][2C]");
   a.N = N; a.C = C; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.pad = pad;
   const int TR = 64 / Wo;
@@ -526,7 +532,7 @@ void pw_bwd(std::vector<py::tuple> calls, int64_t S, int64_t mode, bool need_dx)
     a.dd = ptr_or_null<float>(dd); a.gx = ptr_or_null<float>(gx);
     a.gW = ptr_or_null<float>(gW);
     if (mode == 0) {
-      TORCH_CHECK(a.ain && (!need_dx || a.dd), "mode 0 needs ain (and dd)");
+      TORCH_CHECK((a.ain || !a.gW) && (!need_dx || a.dd), "mode 0 needs ain for a weight gradient (and dd)");
     } else {
       TORCH_CHECK(!need_dx || a.gx, "mode 1 needs gx");
     }
@@ -836,6 +842,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("REP") = kRep;
   m.attr("ZBF16") = kZbf16;  // per-op intermediates stored as bf16 (the _hipkern_zbf16 variant)
   m.def("max_blocks", &max_blocks);
+  m.def("dwpw_split_path", [](int64_t C) { return dwpw_split_path((int)C); });  // such stages need d
   register_xgmi(m);
   register_conv(m);
   register_transformer(m);

@@ -46,6 +46,9 @@ __host__ __device__ __forceinline__ size_t plane_off(int n, int c, int N, int C,
 constexpr int kMaxOps = 8;
 constexpr int kMaxUpd = 4;  // update-only BN layers per combine entry (the separable convs' first stages)
 constexpr int kMaxC = 256;
+// dw-pw stages of 16..64 channels run split: depthwise on channel groups, then the pointwise as an
+// MFMA GEMM over the stored depthwise output d (so d cannot be dropped there)
+constexpr bool dwpw_split_path(int C) { return C % 16 == 0 && C <= 64; }
 // Cross-workgroup sums (BN statistics, BN-backward reductions, weight gradients) go to kRep
 // replicas of the accumulator, workgroup b adding into replica b % kRep: global float atomics
 // execute memory-side and same-address adds serialise, so bounding the adders per address
@@ -85,6 +88,8 @@ struct DwPwFwdArgs {
   const void* x;  // node state (fp32), or the previous stage's z (zt) when it carries an input BN
   BNRef inbn; const float* dw; const float* pw;
   zt* d; zt* z; double* stats;  // stats: kRep replicas of [2C]
+  // d may be null in the fused kernels (its only reader is the pointwise weight gradient); the split
+  // path (depthwise, then the pointwise GEMM over d: C = 16..64) needs it
   int N, C, H, W, Ho, Wo, pad, chunk, use_mfma;
   int variant;  // dwpw_plane_multi_kernel: ((K == 5) * 4 + (dil == 2) * 2 + (S == 2)) * 4 + prebn * 2 + vec
   int nblk;     // dwpw_plane_multi_kernel: workgroups of this entry (grid.x is the max over entries)
@@ -121,6 +126,7 @@ struct CombineBwdArgs {
 
 struct PwBwdArgs {
   GradSrc gs; const float* pw; const zt* ain; const float* x; float* dd; float* gx; float* gW;
+  // ain (mode 0: the stored depthwise output) is read for the weight gradient only: null when gW is
   int gstride;  // floats between gW replicas (0: single accumulator)
   int N, Cin, Cout, CoutTotal, co_off, H, W, Ho, Wo, S, off, mode, need_dx;
   int overwrite;  // mode 1, stride 1: gx = masked grad instead of += (the kernel covers every pixel)

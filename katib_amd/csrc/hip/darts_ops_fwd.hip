@@ -54,7 +54,7 @@ static bool try_dwpw_split_g(const DwPwFwdBatch& b, bool prebn, hipStream_t st, 
       (a.Ho * a.Wo) % 64 != 0 || a.W % 4 != 0)
     return false;
   for (int i = 0; i < b.n; ++i)
-    if (((uintptr_t)b.e[i].x | (uintptr_t)b.e[i].d | (uintptr_t)b.e[i].z) & 15) return false;
+    if (!b.e[i].d || (((uintptr_t)b.e[i].x | (uintptr_t)b.e[i].d | (uintptr_t)b.e[i].z) & 15)) return false;
   const int G = a.C / CG;
   int nb = std::max(1, std::min(a.Ho / 4, 2048 / std::max(a.N * b.n * G, 1)));
   auto band_bytes = [&](int v) {
@@ -132,8 +132,10 @@ static bool dwpw_multi_prep(DwPwMultiBatch& b, bool& fused, int& maxblk, size_t&
     if (a.C != C || a.N != N) return false;
     const int code = a.variant >> 2;
     const int K = (code & 4) ? 5 : 3, DIL = (code & 2) ? 2 : 1, S = (code & 1) ? 2 : 1;
+    // (a null d - fused entries whose pointwise weight gradient nobody wants - is aligned; the split
+    // path's pointwise GEMM reads d, so the binding rejects a null one there)
     const bool aligned = ((((uintptr_t)a.x) | (uintptr_t)a.d | (uintptr_t)a.z) & 15) == 0;
-    if (split && (!aligned || (a.Ho * a.Wo) % 64 != 0 || a.W % 4 != 0)) return false;
+    if (split && (!a.d || !aligned || (a.Ho * a.Wo) % 64 != 0 || a.W % 4 != 0)) return false;
     int nb = std::max(1, std::min(a.Ho / 4, 512 / std::max(N * b.n * G, 1)));
     auto band_bytes = [&](int v) {
       const int BR = (a.Ho + v - 1) / v;

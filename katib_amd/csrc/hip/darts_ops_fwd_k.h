@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(256) dwpw_fwd_kernel(DwPwFwdBatch bt) {
 #pragma unroll
           for (int kx = 0; kx < K; ++kx) acc += wk[ky * K + kx] * src[ky * DIL * IW + kx * DIL];
         sD[c * P + p] = acc;
-        zput(a.d + (((size_t)n * C + c) * Ho + oy0 + ty) * Wo + tx, acc);
+        if (a.d) zput(a.d + (((size_t)n * C + c) * Ho + oy0 + ty) * Wo + tx, acc);
       }
       __syncthreads();
     }
@@ -233,6 +233,9 @@ __device__ __forceinline__ void dwpw_plane_body(const DwPwFwdArgs& a, const int 
   const int HWo = Ho * Wo;
   zt* dn = a.d + ((size_t)n * a.C + c0) * HWo;
   zt* zn = a.z + (size_t)n * C * HWo;
+  // fused: d is stored for the pointwise weight gradient only, null when nobody asks for that
+  // (wave-uniform test); the split path's pointwise GEMM always reads it
+  const bool put_d = !PW || a.d != nullptr;
   const bool vout = VEC && Wo % 4 == 0 && a.vout;
   if (vout) {
     // 4 consecutive output pixels (one row: Wo % 4 == 0) per thread: d and z leave as one 16-byte
@@ -286,7 +289,7 @@ __device__ __forceinline__ void dwpw_plane_body(const DwPwFwdArgs& a, const int 
           }
         }
         d[c] = acc;
-        zst4(dn + (size_t)c * HWo + p, acc);
+        if (put_d) zst4(dn + (size_t)c * HWo + p, acc);
       }
       if (!PW) continue;
 #pragma unroll
@@ -315,7 +318,7 @@ __device__ __forceinline__ void dwpw_plane_body(const DwPwFwdArgs& a, const int 
 #pragma unroll
         for (int kx = 0; kx < K; ++kx) acc += wk[ky * K + kx] * src[ky * DIL * WP + kx * DIL];
       d[c] = acc;
-      zput(dn + (size_t)c * HWo + p, acc);
+      if (put_d) zput(dn + (size_t)c * HWo + p, acc);
     }
     if (!PW) continue;
 #pragma unroll

@@ -58,8 +58,8 @@ __global__ void __launch_bounds__(256) pw_bwd_kernel(PwBwdBatch bt) {
       int ci = i / P, p = i % P;
       int pp = prem + p;
       float v;
-      if (a.mode == 0) {
-        v = z2f(a.ain[((size_t)n * Cin + ci) * HWo + pp]);
+      if (a.mode == 0) {  // the depthwise output feeds the weight gradient only
+        v = a.gW ? z2f(a.ain[((size_t)n * Cin + ci) * HWo + pp]) : 0.f;
       } else {
         int oy = pp / Wo, ox = pp % Wo, iy = oy * a.S + a.off, ix = ox * a.S + a.off;
         v = (iy < a.H && ix < a.W)
@@ -229,7 +229,10 @@ __global__ void __launch_bounds__(256) pw_bwd_px_kernel(PwBwdBatch bt) {
 #pragma unroll
       for (int c = 0; c < CI; ++c) {
         const size_t o = a.mode == 0 ? ((size_t)n * CI + c) * HWo + pp : plane_off(n, c, a.N, CI, a.xnodes, HWo) + pp;
-        av[c] = a.mode == 0 ? zld4(a.ain + o) : *reinterpret_cast<const f4*>(a.x + o);
+        // mode 0: the depthwise output feeds the weight gradient only (ain may be null without one)
+        if (a.mode != 0) av[c] = *reinterpret_cast<const f4*>(a.x + o);
+        else if (want_w) av[c] = zld4(a.ain + o);
+        else av[c] = f4{0.f, 0.f, 0.f, 0.f};
         if (a.mode != 0) {
           av[c].x = fmaxf(av[c].x, 0.f);
           av[c].y = fmaxf(av[c].y, 0.f);
@@ -276,9 +279,9 @@ __global__ void __launch_bounds__(256) pw_bwd_px_kernel(PwBwdBatch bt) {
       dz[c] = bn_bwd_val(a.gs, ((size_t)n * a.CoutTotal + a.co_off + c) * HWo + pp, mean[c], inv[c], wk, m1[c], m2[c]);
     size_t xi0 = 0;
     bool inb = true;
-    if (a.mode == 0) {
+    if (a.mode == 0) {  // the depthwise output feeds the weight gradient only (ain may be null without one)
 #pragma unroll
-      for (int c = 0; c < CI; ++c) av[c] = z2f(a.ain[((size_t)n * CI + c) * HWo + pp]);
+      for (int c = 0; c < CI; ++c) av[c] = want_w ? z2f(a.ain[((size_t)n * CI + c) * HWo + pp]) : 0.f;
     } else {
       const int oy = pp / Wo, ox = pp - oy * Wo, iy = oy * a.S + a.off, ix = ox * a.S + a.off;
       inb = iy < a.H && ix < a.W;

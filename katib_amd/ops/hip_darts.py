@@ -23,7 +23,8 @@ Weight gradients are accumulated by the kernels directly into each weight leaf's
 :func:`register_grad_replicas` (the flat gradient bucket of
 :class:`katib_amd.models.darts_search.DartsSearch`, folded once per backward pass
 with :func:`fold`), so no AccumulateGrad launches follow; detached weights (the
-Hessian passes) skip weight-gradient work. Callers that drive autograd with
+Hessian passes) skip weight-gradient work, and every backward runs only what the
+gradients it was asked for need (:func:`needed_grads`). Callers that drive autograd with
 ``backward(inputs=...)`` must list every weight leaf that requires grad
 (DartsSearch does).
 
@@ -186,8 +187,10 @@ def _world() -> int:
 
 def _fold(segs):
     """Fold the replicas of f64 reductions into replica 0 (under SyncBN: and sum the segments not
-    marked local over the ranks)."""
-    if _SYNC is not None:
+    marked local over the ranks). No segments: no launch; only local ones: no cross-rank fold."""
+    if not segs:
+        return
+    if _SYNC is not None and any(len(sg) < 4 or sg[3] for sg in segs):
         _SYNC.fold(segs)
     else:
         _K.fold_f64([tuple(sg[:3]) for sg in segs])
@@ -331,6 +334,20 @@ DWB_MULTI = True
 EDGE_BWD = False
 
 
+# Needed-gradient pruning of the hand-scheduled backward (module attributes: tests and A/B runs flip
+# them between steps, never inside a capture; profiles/darts_needed_grads_bench_ab.txt).
+# NEEDED_GRADS: only what a backward pass needs runs (needed_grads): the operator backward of an edge
+#   whose source state and own parameters need no gradient, the preprocess layers and the stem BN
+#   backward under the same rule, and their gradient buffers are not issued - in the architect's
+#   finite-difference passes (detached weights, d(alpha) only) that is the alpha-free part of the net.
+# DROP_D: a fused dw-pw stage stores its depthwise output d only when the pointwise weight may get a
+#   gradient (d's only reader); the pointwise backward then gets ain = None.
+# (Handing combine_bwd_reduce no d(alpha) block in the weight-only passes measured inside the run-to-run
+# spread - 4.9185 vs 4.9205 ms per B5 step - and was taken out again: profiles/darts_needed_grads_bench_ab.txt.)
+NEEDED_GRADS = True
+DROP_D = True
+
+
 # A node's pools launched beside its stage-1 dw-pw entries (one launch instead of two per node).
 # Off (module attribute, tests): measured a wash on the B5 step (6.98 vs 6.96 ms,
 # profiles/darts_vec_ab_r04.log) - the pool workgroups (highest blockIdx.y) dispatch after the dw-pw
@@ -437,10 +454,11 @@ class _Edge:
         self.id_done = False
 
 
-def _node_forward(xs, ws, specs, bns, params_list, training, momentum, eps, out=None, extra_fold=()):
+def _node_forward(xs, ws, specs, bns, params_list, training, momentum, eps, out=None, extra_fold=(), grad=True):
     """One node's forward (all kernels of every incoming edge); ``out`` may be a preallocated
-    contiguous buffer (the cell writes each node straight into its concat slot). Returns
-    (out, edges) - ``edges`` is the state :func:`_node_backward` needs."""
+    contiguous buffer (the cell writes each node straight into its concat slot). ``grad``: a
+    backward pass may follow (the caller's grad mode). Returns (out, edges) - ``edges`` is the
+    state :func:`_node_backward` needs."""
     E = len(specs)
     xs = [t.contiguous() for t in xs]
     _selffold(xs[0].device)  # before any producer launch: registers the counter ring on first use
@@ -469,6 +487,14 @@ def _node_forward(xs, ws, specs, bns, params_list, training, momentum, eps, out=
     def new():  # a per-op intermediate (d or z)
         return torch.empty(N, C, Ho, Wo, device=dev, dtype=ZDT)
 
+    keep_d = not DROP_D or bool(_K.dwpw_split_path(C))
+
+    def new_d(pw):
+        """The stored depthwise output of a dw-pw stage: read by the pointwise weight gradient only
+        (and by the pointwise GEMM of the split path, 16..64 channels), so None - the fused kernels
+        then skip the store - unless that weight may get a gradient."""
+        return new() if keep_d or (grad and pw.requires_grad) else None
+
     # ---- stage 1: grouped by (K, dilation, stride, pad)
     dw_groups = defaultdict(list)
     pool_groups = defaultdict(list)
@@ -481,7 +507,7 @@ def _node_forward(xs, ws, specs, bns, params_list, training, momentum, eps, out=
             sl = e.spec.slots.get(prim, ())
             if prim.startswith("separable_convolution"):
                 K = int(prim[-1])
-                d1, z1 = new(), new()
+                d1, z1 = new_d(e.P[prim + ".0.pw"]), new()
                 dw_groups[(K, 1, e.S, K // 2)].append(
                     (e.x, e.P[prim + ".0.dw"], e.P[prim + ".0.pw"], None, d1, z1, st(e, sl[0])))
                 e.saved[prim] = [d1, z1]
@@ -489,7 +515,7 @@ def _node_forward(xs, ws, specs, bns, params_list, training, momentum, eps, out=
                 stage2.append(e.slot0 + sl[1])
             elif prim.startswith("dilated_convolution"):
                 K = int(prim[-1])
-                d, z = new(), new()
+                d, z = new_d(e.P[prim + ".pw"]), new()
                 dw_groups[(K, 2, e.S, (K // 2) * 2)].append(
                     (e.x, e.P[prim + ".dw"], e.P[prim + ".pw"], None, d, z, st(e, sl[0])))
                 e.zs[k], e.bns[k] = z, e.refs[sl[0]]
@@ -546,7 +572,7 @@ def _node_forward(xs, ws, specs, bns, params_list, training, momentum, eps, out=
                 K = int(prim[-1])
                 sl = e.spec.slots[prim]
                 d1, z1 = e.saved[prim]
-                d2, z2 = new(), new()
+                d2, z2 = new_d(e.P[prim + ".1.pw"]), new()
                 inbn = _unfolded(e.refs[sl[0]]) if defer else e.refs[sl[0]]
                 s2_groups[K].append((z1, e.P[prim + ".1.dw"], e.P[prim + ".1.pw"], inbn, d2, z2, st(e, sl[1])))
                 e.upd.append(e.refs[sl[0]])
@@ -570,34 +596,49 @@ def _node_forward(xs, ws, specs, bns, params_list, training, momentum, eps, out=
     return out, edges
 
 
-def _node_backward(edges, training, C, dout, gx_of, take_first, sinks, pkey, cell_gw=None):
+def _node_backward(edges, training, C, dout, gx_of, take_first, sinks, pkey, cell_gw=None, live=None,
+                   alpha_need=True):
     """One node's backward. ``gx_of(i)`` is the input-gradient buffer of edge i (edges of
     different nodes that read the same state share one buffer); ``take_first(i)`` is True for
     the first kernel that writes it (it overwrites instead of accumulating, so no memset);
     weight gradients go through ``sinks`` under the keys ``pkey(edge, name)``. Buffers no
     kernel wrote (an edge whose only primitive is ``none``) are the caller's to zero.
-    The alpha-weight gradients stay in ``edge.gw`` (f64, folded)."""
-    E = len(edges)
+    ``live[i]`` (default: all): edge i's operator backward - everything after combine_bwd_reduce -
+    runs (:func:`_edge_live`); an edge that is not live gets no input-gradient buffer, no
+    temporaries and no BN-backward fold segment, and keeps its combine_bwd_reduce entry only for
+    d(alpha) (``alpha_need``). The alpha-weight gradients stay in ``edge.gw`` (f64 replicas, folded
+    unless ``cell_gw`` collects them; None for an edge without an entry)."""
     dout = dout.contiguous()
     dev = dout.device
+    if live is None:
+        live = [True] * len(edges)
+    for e in edges:
+        e.gw = None
+    entries = [e for e in edges if alpha_need or live[e.i]]  # combine_bwd_reduce entries
+    edges = [e for e in edges if live[e.i]]  # below: the operator backward of the live edges
+    if not entries:
+        return
 
     def sink(e, name):
         return sinks.get(e.P[name], pkey(e, name))
 
     # ---- BN-backward sums and d(alpha) for every edge, one fold
     sizes = []
-    for e in edges:
+    for e in entries:
         e.nred = (len(e.zl) + 1) * C + 1
         sizes.append(REP * (e.nred + e.w.numel()))
     buf = zeros64(sum(sizes), dev)
     o = 0
-    calls, segs = [], []
-    for e, sz in zip(edges, sizes):
+    calls, segs, gsegs = [], [], []
+    for e, sz in zip(entries, sizes):
         e.red = buf[o:o + REP * e.nred]
         e.gw = buf[o + REP * e.nred:o + sz]
         o += sz
         calls.append((dout, e.zl, e.bl, e.x if e.id_idx >= 0 else None, e.red, e.widx, e.id_idx, e.gw))
-        segs += [(e.red, e.nred, e.nred), (e.gw, e.w.numel(), e.w.numel(), False)]  # d alpha stays per rank
+        if live[e.i]:  # nobody reads the BN-backward sums of an edge whose operator backward is skipped
+            segs.append((e.red, e.nred, e.nred))
+        gsegs.append((e.gw, e.w.numel(), e.w.numel(), False))  # d alpha stays per rank
+        segs.append(gsegs[-1])
     _launch("combine_bwd_reduce", calls)
     # deferred: the pointwise backward right below sums the replicas itself and this fold joins
     # the separable second stages' fold (or runs after that pointwise launch)
@@ -606,9 +647,9 @@ def _node_backward(edges, training, C, dout, gx_of, take_first, sinks, pkey, cel
     # folds nothing: the d(alpha) segments go to the cell, which folds them once (if it needs them)
     nofold = defer and cell_gw is not None and not EDGE_BWD
     if nofold:
-        cell_gw.extend(segs[1::2])
+        cell_gw.extend(gsegs)
     if not _selffold(dev) and not defer:
-        _fold(segs if FOLD else segs[1::2])  # the d(alpha) segments are always folded
+        _fold(segs if FOLD else gsegs)  # the d(alpha) segments are always folded
 
     r_early = REP if defer else _R  # replicas the pointwise backward below reads
     r_late = REP if nofold else _R  # ... and the pool / stride-2 skip backward further down
@@ -617,7 +658,7 @@ def _node_backward(edges, training, C, dout, gx_of, take_first, sinks, pkey, cel
         j = e.widx.index(k)
         return (dout, z, e.red[:C], e.red[(1 + j) * C:(2 + j) * C], e.bl[j], e.w, k, rep, e.nred)
 
-    gxs = [gx_of(e.i) for e in edges]
+    gxs = {e.i: gx_of(e.i) for e in edges}
 
     # dilated convs' pointwise backward is independent of the separable chain: its entries join
     # the separable second stages' pw_bwd batch (one launch instead of two)
@@ -625,7 +666,7 @@ def _node_backward(edges, training, C, dout, gx_of, take_first, sinks, pkey, cel
     pwd, dd_of = [], {}
     for e, k, prim in dils:
         d, z = e.saved[prim]
-        dd = torch.empty(d.shape, device=dev)  # gradients stay fp32
+        dd = torch.empty(z.shape, device=dev)  # gradients stay fp32 (d: None without a pointwise weight gradient)
         dd_of[(e.i, prim)] = dd
         g, gst = sink(e, prim + ".pw")
         pwd.append((src(e, k, z, r_early), e.P[prim + ".pw"], d, e.x, dd, None, g, 0, 0, gst))
@@ -641,7 +682,7 @@ def _node_backward(edges, training, C, dout, gx_of, take_first, sinks, pkey, cel
         for n, (e, k, prim) in enumerate(seps):
             K = int(prim[-1])
             d1, z1, d2, z2 = e.saved[prim]
-            dd2 = torch.empty(d2.shape, device=dev)
+            dd2 = torch.empty(z2.shape, device=dev)
             g, gst = sink(e, prim + ".1.pw")
             pw2.append((src(e, k, z2, r_early), e.P[prim + ".1.pw"], d2, z1, dd2, None, g, 0, 0, gst))
             g1 = torch.empty(z1.shape, device=dev)
@@ -668,7 +709,7 @@ def _node_backward(edges, training, C, dout, gx_of, take_first, sinks, pkey, cel
             g1, r1 = e.saved[prim + "/g1"]
             b1 = e.refs[e.spec.slots[prim][0]]
             gs1 = (g1, z1, r1[:C] if training else None, r1[C:2 * C] if training else None, b1, None, 0, r_late, 2 * C)
-            dd1 = torch.empty(d1.shape, device=dev)
+            dd1 = torch.empty(z1.shape, device=dev)
             e.saved[prim + "/dd1"] = dd1
             g, gst = sink(e, prim + ".0.pw")
             pw1.append((gs1, e.P[prim + ".0.pw"], d1, e.x, dd1, None, g, 0, 0, gst))
@@ -802,13 +843,13 @@ def _node_backward(edges, training, C, dout, gx_of, take_first, sinks, pkey, cel
 class _MixedNode(torch.autograd.Function):
     @staticmethod
     def forward(ctx, meta, *flat):
-        specs, bns, training, momentum, eps, nparams = meta
+        specs, bns, training, momentum, eps, nparams, grad = meta
         E = len(specs)
         params, off = [], 2 * E
         for n in nparams:
             params.append(flat[off:off + n])
             off += n
-        out, edges = _node_forward(flat[:E], flat[E:2 * E], specs, bns, params, training, momentum, eps)
+        out, edges = _node_forward(flat[:E], flat[E:2 * E], specs, bns, params, training, momentum, eps, grad=grad)
         ctx.meta = (edges, training, out.shape[1])
         ctx.save_for_backward(*flat)
         return out
@@ -823,7 +864,9 @@ class _MixedNode(torch.autograd.Function):
         for e in edges:
             pbase.append(acc)
             acc += len(e.spec.pnames)
-        gxs = [torch.empty_like(e.x) for e in edges]
+        need = ctx.needs_input_grad
+        live = [_edge_live(e, need[1 + e.i]) for e in edges]
+        gxs = [torch.empty_like(e.x) if lv else None for e, lv in zip(edges, live)]
         first = [True] * E
 
         def take_first(i):
@@ -832,14 +875,14 @@ class _MixedNode(torch.autograd.Function):
             return f
 
         _node_backward(edges, training, C, dout, lambda i: gxs[i], take_first, sinks,
-                       lambda e, name: pbase[e.i] + e.spec.pidx[name])
+                       lambda e, name: pbase[e.i] + e.spec.pidx[name], None, live, any(need[1 + E:1 + 2 * E]))
         for i in range(E):
-            if first[i]:  # an edge whose only primitive is "none"
+            if first[i] and live[i]:  # an edge whose only primitive is "none"
                 gxs[i].zero_()
         grads = [None] * len(flat)
         for i, e in enumerate(edges):
-            grads[i] = gxs[i] if ctx.needs_input_grad[1 + i] else None
-            grads[E + i] = e.gw[:e.w.numel()].to(e.w.dtype) if ctx.needs_input_grad[1 + E + i] else None
+            grads[i] = gxs[i] if need[1 + i] else None
+            grads[E + i] = e.gw[:e.w.numel()].to(e.w.dtype) if need[1 + E + i] else None
         sinks.finish(grads)
         return (None, *grads)
 
@@ -848,7 +891,7 @@ def mixed_node(xs: Sequence[torch.Tensor], ws: Sequence[torch.Tensor], specs: Se
                bns: Sequence[List[Tuple[torch.Tensor, torch.Tensor]]], params: Sequence[Sequence[torch.Tensor]],
                training: bool, momentum: float = 0.1, eps: float = 1e-5):
     """sum over edges e of sum_k ws[e]_k * op_k(xs[e]); ``params[e]`` ordered as ``specs[e].pnames``."""
-    meta = (list(specs), list(bns), training, momentum, eps, [len(p) for p in params])
+    meta = (list(specs), list(bns), training, momentum, eps, [len(p) for p in params], torch.is_grad_enabled())
     flat = list(xs) + list(ws) + [p for ps in params for p in ps]
     return _MixedNode.apply(meta, *flat)
 
@@ -964,7 +1007,35 @@ class CellSpec:
         self.index = {n: i for i, n in enumerate(self.names)}
 
 
-def _cell_fwd(spec, s0, s1, wts, P, bn_of, training, momentum, eps):
+def needed_grads(spec: CellSpec, need0: bool, need1: bool, wreq, alpha: bool) -> List[bool]:
+    """Which states of a cell need their gradient in a backward pass: ``[t0, t1, node 0, ...]`` (the
+    two preprocessed inputs, then every node). ``need0`` / ``need1``: the cell's inputs s0 / s1 need
+    one; ``wreq(name)``: that parameter requires a gradient (what :meth:`_Sinks.get` tests);
+    ``alpha``: the softmax weights of this cell type do. A state needs a gradient if and only if
+    something its value depends on does - a parameter, the softmax weights, or a state that needs
+    one itself. Pure bookkeeping on the static :class:`CellSpec`: no tensors, no launches."""
+    need = [need0 or any(wreq(n) for n in spec.pre0[1]), need1 or any(wreq(n) for n in spec.pre1[1])]
+    for node in spec.nodes:
+        need.append(any(alpha or need[src] or any(wreq(n) for n in pnames) for _, pnames, _, src, _ in node))
+    return need
+
+
+def network_needed_grads(spec: "NetSpec", wreq, alpha_n: bool, alpha_r: bool):
+    """:func:`needed_grads` over the whole supernet: (stem output needs a gradient, per cell its
+    ``needed_grads`` list). A cell output needs a gradient if any of its nodes does; the stem
+    output if a stem parameter requires one."""
+    need = [any(wreq(n) for n in spec.stem[:3])]
+    i0 = i1 = 0
+    cells = []
+    for cspec, red in zip(spec.cells, spec.reduce):
+        c = needed_grads(cspec, need[i0], need[i1], wreq, alpha_r if red else alpha_n)
+        cells.append(c)
+        need.append(any(c[2:]))
+        i0, i1 = i1, len(need) - 1
+    return need[0], cells
+
+
+def _cell_fwd(spec, s0, s1, wts, P, bn_of, training, momentum, eps, grad=True):
     """A DARTS cell forward on the HIP kernels: preprocess(s0), preprocess(s1) (each input
     [N][C][H][W] or node-major), every node. Returns (O, state): O = the node outputs,
     node-major [nodes][N][C][H][W] - the cell output is kept as its nodes' buffers, never
@@ -994,13 +1065,19 @@ def _cell_fwd(spec, s0, s1, wts, P, bn_of, training, momentum, eps):
         bns = [[bn_of(b) for b in bnames] for _, _, bnames, _, _ in node]
         plist = [[P[n] for n in pnames] for _, pnames, _, _, _ in node]
         out, edges = _node_forward(xs, ws, specs, bns, plist, training, momentum, eps, out=O[i],
-                                   extra_fold=late if i == 0 else ())
+                                   extra_fold=late if i == 0 else (), grad=grad)
         states.append(out)
         node_states.append(edges)
-    return O, (spec, training, st0, st1, node_states, states, wts)
+    return O, (spec, training, st0, st1, node_states, states, wts, P)
 
 
-def _cell_bwd(state, gO, sinks, pkey, gx0, first0, gx1, first1, need0, need1, alpha_rows=None):
+def _edge_live(e, src_need: bool) -> bool:
+    """An edge's operator backward (everything after combine_bwd_reduce) runs for its source state's
+    gradient or for a parameter of its own that requires one."""
+    return not NEEDED_GRADS or src_need or any(p.requires_grad for p in e.P.values())
+
+
+def _cell_bwd(state, gO, sinks, pkey, gx0, first0, gx1, first1, need0, need1, alpha_rows=None, alpha_need=True):
     """The cell backward: ``gO`` = gradient of the node outputs (node-major, overwritten by the
     nodes' input-gradient kernels as scratch), nodes in reverse with one gradient buffer per cell
     state (the first kernel writing a buffer overwrites it, later ones accumulate), then both
@@ -1008,19 +1085,31 @@ def _cell_bwd(state, gO, sinks, pkey, gx0, first0, gx1, first1, need0, need1, al
     ``first1``. Weight gradients through ``sinks`` under ``pkey(name)``. ``alpha_rows`` (a list):
     the edges' replicated d(softmax weight) go there as (f64 replicas, rstride, weight row) for the
     alpha-gradient kernel; otherwise they are folded and returned as a [rows, K] tensor.
-    Returns (gs0, gs1, d softmax weights or None)."""
-    spec, training, st0, st1, node_states, states, wts = state
+    ``alpha_need``: this cell type's softmax weights need a gradient. Only what the pass needs runs
+    (:func:`needed_grads`): a node that needs no gradient is skipped, an edge's operator backward
+    runs only for a source state or a parameter of its own that needs one, a preprocess layer only
+    for its input or its weights. Returns (gs0, gs1, d softmax weights or None)."""
+    spec, training, st0, st1, node_states, states, wts, P = state
     nn_ = len(spec.nodes)
+    if NEEDED_GRADS:
+        need = needed_grads(spec, need0, need1, lambda n: P[n].requires_grad, alpha_need)
+    else:
+        need = [True] * (2 + nn_)
     gS = [None, None] + [gO[i] for i in range(nn_)]
     first = [True, True] + [False] * nn_
     ga_rows = [None] * nn_
     cell_gw = []  # the nodes' unfolded d(alpha) replicas
     for i in reversed(range(nn_)):
+        if not need[2 + i]:
+            continue
         node = spec.nodes[i]
         edges = node_states[i]
         srcs = [src for _, _, _, src, _ in node]
-        for src in srcs:
-            if gS[src] is None:
+        live = [_edge_live(e, need[src]) for e, src in zip(edges, srcs)]
+        for src, lv in zip(srcs, live):
+            # (a live edge from a state that needs no gradient - a parameter of its own does - still
+            # writes its input gradient: into a buffer nobody reads)
+            if lv and gS[src] is None:
                 gS[src] = torch.empty_like(states[src])
 
         def take_first(k, srcs=srcs):
@@ -1029,23 +1118,27 @@ def _cell_bwd(state, gO, sinks, pkey, gx0, first0, gx1, first1, need0, need1, al
             return f
 
         _node_backward(edges, training, spec.C, gS[2 + i], lambda k, srcs=srcs: gS[srcs[k]], take_first, sinks,
-                       lambda e, name, node=node: pkey(node[e.i][1][e.spec.pidx[name]]), cell_gw)
+                       lambda e, name, node=node: pkey(node[e.i][1][e.spec.pidx[name]]), cell_gw, live, alpha_need)
         if alpha_rows is not None:
             for e, (_, _, _, _, row) in zip(edges, node):
-                alpha_rows.append((e.gw, e.w.numel(), wts[row], row))
-        else:
+                if e.gw is not None:
+                    alpha_rows.append((e.gw, e.w.numel(), wts[row], row))
+        elif alpha_need:
             ga_rows[i] = [e.gw[:wts.shape[1]] for e in edges]
-    for j in (0, 1):
+    gs = [None, None]
+    for j, (st, needx, gx, fst, pre) in enumerate(((st0, need0, gx0, first0, spec.pre0),
+                                                   (st1, need1, gx1, first1, spec.pre1))):
+        if not need[j]:  # neither its input nor its weights need a gradient: nothing to launch
+            continue
         if first[j]:  # only "none" primitives read this state
             gS[j] = torch.zeros_like(states[j])
-    gs0 = _stdconv_backward(st0, gS[0], need0, sinks, tuple(pkey(n) for n in spec.pre0[1]) + (None,), gx0, first0)
-    gs1 = _stdconv_backward(st1, gS[1], need1, sinks, tuple(pkey(n) for n in spec.pre1[1]) + (None,), gx1, first1)
+        gs[j] = _stdconv_backward(st, gS[j], needx, sinks, tuple(pkey(n) for n in pre[1]) + (None,), gx, fst)
     gw = None
-    if alpha_rows is None:
+    if alpha_rows is None and alpha_need:
         if cell_gw:
             _K.fold_f64(cell_gw)  # d alpha: per rank
         gw = torch.cat([g for rows in ga_rows for g in rows]).view(wts.shape).to(torch.float32)
-    return gs0, gs1, gw
+    return gs[0], gs[1], gw
 
 
 class _Cell(torch.autograd.Function):
@@ -1056,9 +1149,9 @@ class _Cell(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, meta, s0, s1, wts, *params):
-        spec, bn_of, training, momentum, eps = meta
+        spec, bn_of, training, momentum, eps, grad = meta
         P = dict(zip(spec.names, params))
-        O, state = _cell_fwd(spec, s0, s1, wts, P, bn_of, training, momentum, eps)
+        O, state = _cell_fwd(spec, s0, s1, wts, P, bn_of, training, momentum, eps, grad)
         nn_, N, C, Ho, Wo = O.shape
         y = O.permute(1, 0, 2, 3, 4).reshape(N, nn_ * C, Ho, Wo)
         ctx.cell = state
@@ -1081,7 +1174,7 @@ class _Cell(torch.autograd.Function):
         need = ctx.needs_input_grad
         grads = [None] * (4 + len(params))
         gs0, gs1, gw = _cell_bwd(state, gO, sinks, lambda n: 4 + spec.index[n], None, True, None, True, need[1],
-                                 need[2])
+                                 need[2], None, need[3])
         grads[1], grads[2] = gs0, gs1
         if need[3]:
             grads[3] = gw
@@ -1094,7 +1187,7 @@ def cell_forward(spec: CellSpec, s0, s1, wts, params: Sequence[torch.Tensor], bn
     """A DARTS cell on the HIP kernels (see :class:`_Cell`). ``wts`` [rows, K] are the
     softmax weights of this cell type; ``params`` follow ``spec.names``; ``bn_of(name)`` gives
     the (running mean, running var) views of a BN layer."""
-    return _Cell.apply((spec, bn_of, training, momentum, eps), s0, s1, wts, *params)
+    return _Cell.apply((spec, bn_of, training, momentum, eps, torch.is_grad_enabled()), s0, s1, wts, *params)
 
 
 def relu_conv_bn(x, w, rm, rv, training, momentum=0.1, eps=1e-5):
@@ -1364,7 +1457,7 @@ class _Network(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, meta, x, y, an, ar, *params):
-        spec, bn_of, training, momentum, eps = meta
+        spec, bn_of, training, momentum, eps, grad = meta
         P = dict(zip(spec.names, params))
         dev = x.device
         mats, outs = [an], [torch.empty_like(an)]
@@ -1387,7 +1480,8 @@ class _Network(torch.autograd.Function):
         cells = []
         i0 = i1 = 0
         for cspec, red in zip(spec.cells, spec.reduce):
-            O, st = _cell_fwd(cspec, tensors[i0], tensors[i1], wr if red else wn, P, bn_of, training, momentum, eps)
+            O, st = _cell_fwd(cspec, tensors[i0], tensors[i1], wr if red else wn, P, bn_of, training, momentum, eps,
+                              grad)
             tensors.append(O)
             cells.append((st, i0, i1, len(tensors) - 1, red))
             i0, i1 = i1, len(tensors) - 1
@@ -1419,21 +1513,37 @@ class _Network(torch.autograd.Function):
 
         def key(n):
             return 5 + spec.index[n]
-        g, first = {last: torch.empty_like(tensors[last])}, {last: False}
+        # which states need a gradient at all (static per pass: the same for every rank and for both
+        # recorded passes of a stacked pair): tensors[0] = the stem output, then the cell outputs
+        alpha = {False: bool(need[3]), True: ar is not None and bool(need[4])}
+        if NEEDED_GRADS:
+            stem_need, plans = network_needed_grads(spec, lambda n: P[n].requires_grad, alpha[False], alpha[True])
+            needT = [stem_need] + [any(c[2:]) for c in plans]
+        else:
+            needT = [True] * len(tensors)
+        g, first = {}, {}
+        if needT[last]:
+            g[last], first[last] = torch.empty_like(tensors[last]), False
         hw, hb = spec.head
         gw, sw = sinks.get(P[hw], key(hw)) if need[key(hw)] else (None, 0)
         gb, sb = sinks.get(P[hb], key(hb)) if need[key(hb)] else (None, 0)
-        _K.head_bwd(tensors[last], dl, pooled, P[hw], gloss.reshape(()).contiguous().float(), g[last], gw, sw, gb, sb)
+        if needT[last] or gw is not None or gb is not None:
+            _K.head_bwd(tensors[last], dl, pooled, P[hw], gloss.reshape(()).contiguous().float(), g.get(last), gw, sw,
+                        gb, sb)
         rows = []
         for st, i0, i1, io, red in reversed(cells):
+            if not needT[io]:  # no node of this cell needs a gradient (so neither do its inputs)
+                continue
             for i in (i0, i1):
-                if i not in g:
+                if needT[i] and i not in g:
                     g[i], first[i] = torch.empty_like(tensors[i]), True
-            f0 = first[i0]
-            f1 = first[i1] and i1 != i0  # the first cell's two inputs are both the stem output
+            f0 = first.get(i0, False)
+            f1 = first.get(i1, False) and i1 != i0  # the first cell's two inputs are both the stem output
             cell_rows = []
-            _cell_bwd(st, g[io], sinks, key, g[i0], f0, g[i1], f1, True, True, cell_rows)
-            first[i0] = first[i1] = False
+            _cell_bwd(st, g[io], sinks, key, g.get(i0), f0, g.get(i1), f1, needT[i0], needT[i1], cell_rows, alpha[red])
+            for i in (i0, i1):
+                if needT[i]:
+                    first[i] = False
             rows += [(r, red) for r in cell_rows]
         # d(alpha) straight into the leaves' gradient rows (or into returned tensors)
         dst = {}
@@ -1448,8 +1558,8 @@ class _Network(torch.autograd.Function):
         if ents:
             _alpha_grad(ents)
         conv, gamma, beta, _ = spec.stem
-        if training and st_stem is not None and 0 in g:
-            flags = (False, need[key(conv)], need[key(gamma)], need[key(beta)])
+        flags = (False, need[key(conv)], need[key(gamma)], need[key(beta)])
+        if training and st_stem is not None and 0 in g and (any(flags) or not NEEDED_GRADS):
             _stem_bwd(st_stem, g[0], sinks, (key(conv), key(gamma), key(beta)), flags)
         sinks.finish(grads)
         return tuple(grads)
@@ -1470,7 +1580,7 @@ class _Network(torch.autograd.Function):
 _MERGE_CAP = {"dwpw_fwd": 16, "pw_fwd": 32, "pool_fwd": 16, "combine_bwd_reduce": 8, "pw_bwd": 32, "dw_bwd": 40,
               "pool_bwd": 16, "dw_bwd_multi": 40, "dwpw_fwd_multi": 40, "pool_fwd_multi": 16,
               "pool_bwd_multi": 16, "fold_f64": 128, "alpha_grad": 128, "__sync_fold__": 64}
-_QUERIES = {"selffold_ready", "max_blocks", "stamps_compiled", "REP", "ZBF16", "OPTIM_MAX_PARTS"}
+_QUERIES = {"selffold_ready", "max_blocks", "stamps_compiled", "REP", "ZBF16", "OPTIM_MAX_PARTS", "dwpw_split_path"}
 
 
 class _Recorder:
@@ -1572,4 +1682,4 @@ def network_loss(spec: NetSpec, x, y, params: Sequence[torch.Tensor], an, ar, bn
     """(mean cross-entropy, logits) of the DARTS supernet on the HIP kernels as one Function
     (:class:`_Network`); ``an`` / ``ar``: the [rows, K] alpha matrices of the normal / reduction
     cells (``ar`` None for a one-layer net); ``params`` ordered as ``spec.names``."""
-    return _Network.apply((spec, bn_of, training, momentum, eps), x, y, an, ar, *params)
+    return _Network.apply((spec, bn_of, training, momentum, eps, torch.is_grad_enabled()), x, y, an, ar, *params)
