@@ -11,7 +11,8 @@ the images so that training makes measurable progress.
 ``cifar10_from_dir`` reads the CIFAR-10 binary version from a local directory instead and keeps
 the raw bytes in HBM (packed ``[N, 32, 32, 4]`` uint8, 205 MB for the train split); the batch
 gather normalises through a 256-entry table per channel (``ops/augment.py``). With an ``AugSpec``
-the same gather also crops and flips - the reference trial's ``train_transform``.
+the same gather also crops and flips - the reference trial's ``train_transform`` - or, in
+translation mode, flips and translates: the ENAS reference child's Keras augmentation.
 """
 
 from __future__ import annotations
@@ -115,9 +116,12 @@ class PackedU8Dataset:
         return DeviceSubset(self, start, end)
 
 
-def cifar10_from_dir(root: str, device, split: str = "train", limit: int = 0) -> PackedU8Dataset:
+def cifar10_from_dir(root: str, device, split: str = "train", limit: int = 0,
+                     lut: Optional[torch.Tensor] = None) -> PackedU8Dataset:
     """The CIFAR-10 binary version under ``root`` (numpy / torch only: no pickle, no torchvision).
-    ``limit`` keeps the first ``limit`` images."""
+    ``limit`` keeps the first ``limit`` images. ``lut [3, 256]`` replaces the default table (the
+    per-channel mean / std normalisation of the DARTS and ResNet trials); the ENAS child passes
+    ``byte / 255``."""
     if split not in CIFAR10_FILES:
         raise ValueError("cifar10_from_dir: split must be 'train' or 'test', got %r" % (split,))
     names = CIFAR10_FILES[split]
@@ -142,5 +146,6 @@ def cifar10_from_dir(root: str, device, split: str = "train", limit: int = 0) ->
     packed = torch.zeros(n, 32, 32, 4, dtype=torch.uint8)
     packed[..., :3] = rec[:, 1:].view(n, 3, 32, 32).permute(0, 2, 3, 1)
     dev = torch.device(device)
-    return PackedU8Dataset(packed.to(dev), rec[:, 0].to(torch.int64).to(dev),
-                           cifar_lut(CIFAR10_MEAN, CIFAR10_STD).to(dev), 10)
+    if lut is None:
+        lut = cifar_lut(CIFAR10_MEAN, CIFAR10_STD)
+    return PackedU8Dataset(packed.to(dev), rec[:, 0].to(torch.int64).to(dev), lut.to(dev), 10)

@@ -21,6 +21,19 @@ on the NHWC bf16 HIP kernels (``ops/batchnorm.py``, channel counts that are mult
 (``ops/pool.py``), synthetic CIFAR-10-shaped data in HBM, and data parallelism
 over the trial's GPUs (``WORLD_SIZE`` ranks, RCCL all-reduce of the flat gradient)
 in place of ``tf.distribute.MirroredStrategy``.
+
+Data and augmentation (``RunTrial.py:71-96``). ``--data-dir DIR`` trains on the CIFAR-10 binary
+version found there (``workloads/data.py: cifar10_from_dir``; train split capped by ``--num-train``)
+and validates on ``test_batch.bin`` (capped by ``--num-valid``), as the reference validates on
+``x_test``; the raw bytes stay in HBM and the batch gather scales them by 1 / 255 through a table.
+``--augment {auto,0,1}`` turns on the reference's ``RandomFlip('horizontal')`` +
+``RandomTranslation(0.1, 0.1)`` for the training batches - flip, then a bilinear translation by up to
+10 % of the image with reflected borders, fused into the on-device batch gather
+(``ops/augment.py``, translation mode; the draw is keyed by data-set index, stream 0 and the epoch
+number, so every sharding sees the same images); ``auto`` is on with ``--data-dir`` and off on
+synthetic data. The gather writes the static ``[B, H, W, C]`` bf16 buffer ``ChildTrainer.xb`` inside
+the captured step; validation is never augmented. With neither flag the step is the plain
+``index_select`` step.
 """
 
 from __future__ import annotations
@@ -38,6 +51,7 @@ from ..ops import batchnorm as hbn
 from ..ops import conv as hconv
 from ..ops import pool as hpool
 from ..ops import dwconv as hdw
+from ..ops.augment import PLAIN, AugSpec, augment_gather, cifar_lut
 from .common import CapturedStep, Timer, device, global_avg_pool, pattern_images, report
 
 
@@ -188,15 +202,24 @@ def parse_args(argv):
     # HIP-graph-captured train step (default); --capture 0 runs it eagerly
     p.add_argument("--capture", type=int, default=1)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--data-dir", type=str, default="",
+                   help="directory with the CIFAR-10 binary version (train split for training, test_batch.bin "
+                        "for validation); default: the synthetic set")
+    p.add_argument("--augment", type=str, default="auto", choices=["auto", "0", "1"],
+                   help="random horizontal flip + translation by up to 10 %% (bilinear, reflected borders) in the "
+                        "training batch gather; auto = on with --data-dir")
     return p.parse_args(argv)
 
 
 class ChildTrainer:
     """The trial's model, optimizer and (optionally HIP-graph-captured) train step; ``main``
-    drives it epoch by epoch, tests drive it step by step."""
+    drives it epoch by epoch, tests drive it step by step. With ``data_dir`` and / or ``augment``
+    the training batch comes from ``augment_gather`` into the static buffer ``xb`` (``epoch_t``, the
+    device epoch of the draws, is filled by the driver once per epoch); with neither, from
+    ``index_select``."""
 
     def __init__(self, arch, nn_config, num_train=50000, num_valid=10000, batch_size=128, capture=True, seed=0,
-                 comm=None):
+                 comm=None, data_dir="", augment=False):
         from ..parallel.comm import Comm
 
         dev = device()
@@ -206,10 +229,37 @@ class ChildTrainer:
         self.dev, self.cuda = dev, cuda
         mf = torch.channels_last if cuda else torch.contiguous_format
         c, h, w = _chw(nn_config["input_sizes"])
-        x, y = pattern_images(num_train + num_valid, (c, h, w), seed=777, dev=dev,
-                              dtype=torch.bfloat16 if cuda else torch.float32, noise=2.0)
-        x = x.contiguous(memory_format=mf)
-        self.tx, self.ty, self.vx, self.vy = x[:num_train], y[:num_train], x[num_train:], y[num_train:]
+        self.lut = self.epoch_t = None
+        if data_dir:
+            from .data import cifar10_from_dir
+
+            if (c, h, w) != (3, 32, 32):
+                raise ValueError("--data-dir: CIFAR-10 is 32x32x3, nn_config input_sizes give %dx%dx%d" % (h, w, c))
+            # byte / 255 for training and validation alike. Documented divergence: the reference
+            # divides its training images by 255 twice (in numpy, RunTrial.py:74, and again in the
+            # Rescaling layer of its augmentation pipeline) and its validation images once; not
+            # reproduced here.
+            self.lut = cifar_lut((0.0, 0.0, 0.0), (1.0, 1.0, 1.0)).to(dev)
+            tds = cifar10_from_dir(data_dir, dev, "train", limit=num_train, lut=self.lut)
+            vds = cifar10_from_dir(data_dir, dev, "test", limit=num_valid, lut=self.lut)
+            num_train = tds.n
+            self.tx, self.ty, self.vx, self.vy = None, tds.y, None, vds.y
+            self.src, self.vsrc = tds.x, vds.x  # packed [N, 32, 32, 4] uint8
+        else:
+            x, y = pattern_images(num_train + num_valid, (c, h, w), seed=777, dev=dev,
+                                  dtype=torch.bfloat16 if cuda else torch.float32, noise=2.0)
+            x = x.contiguous(memory_format=mf)
+            self.tx, self.ty, self.vx, self.vy = x[:num_train], y[:num_train], x[num_train:], y[num_train:]
+            # the gather's source: the channels-last bf16 set as [N, H, W, C] (fp32 [N, C, H, W] on the CPU)
+            self.src = self.tx.permute(0, 2, 3, 1) if cuda else self.tx
+        gather = bool(data_dir) or bool(augment)
+        if augment:
+            self.epoch_t = torch.zeros(1, dtype=torch.int32, device=dev)
+            spec = AugSpec(pad=0, flip=True, translate=0.1, seed=seed, stream=0, epoch=self.epoch_t)
+        else:
+            spec = PLAIN
+        if gather:
+            self.xb = torch.empty(batch_size, h, w, c, dtype=torch.bfloat16, device=dev)
         self.model = model = ChildNet(arch, nn_config).to(dev).to(memory_format=mf)
         comm = self.comm
         if comm.world_size > 1:  # every rank starts from rank 0's weights
@@ -228,7 +278,11 @@ class ChildTrainer:
         tx, ty = self.tx, self.ty
 
         def train_step():
-            xb, yb = tx.index_select(0, idx), ty.index_select(0, idx)
+            if gather:  # flip + translate (or the plain, table-normalising gather) into the static buffer
+                xb = self._nchw(augment_gather(self.src, idx, spec, self.lut, out=self.xb, nhwc=True))
+            else:
+                xb = tx.index_select(0, idx)
+            yb = ty.index_select(0, idx)
             with torch.autocast(device_type=dev.type, dtype=torch.bfloat16, enabled=cuda):
                 logits = model(xb)
             loss = F.cross_entropy(logits.float(), yb)
@@ -244,6 +298,12 @@ class ChildTrainer:
         # channels-last bf16 tensors (GAP mean, bias sums), now HIP kernels / a pooling window
         self.step_fn = CapturedStep(train_step, enabled=bool(capture) and comm.world_size == 1, no_miopen=True)
 
+    def _nchw(self, x: torch.Tensor) -> torch.Tensor:
+        """A gathered ``[B, H, W, C]`` bf16 batch as the model's input: the channels-last NCHW view
+        of the same memory on a GPU, fp32 on the CPU."""
+        x = x.permute(0, 3, 1, 2)
+        return x if self.cuda else x.float()
+
     def step(self, batch_idx: torch.Tensor):
         self.idx.copy_(batch_idx)
         self.step_fn()
@@ -257,13 +317,22 @@ class ChildTrainer:
     def validate(self, num_valid=None, chunk=1000):
         """Eager eval-mode pass over the validation split -> (mean loss, accuracy)."""
         self.model.eval()
-        n = self.vx.shape[0] if num_valid is None else num_valid
+        if self.vx is None:  # raw bytes: the plain (normalising) gather, never augmented
+            n = self.vy.shape[0] if num_valid is None else min(num_valid, self.vy.shape[0])
+        else:
+            n = self.vx.shape[0] if num_valid is None else num_valid
         vl, vc = 0.0, 0.0
         with torch.autocast(device_type=self.dev.type, dtype=torch.bfloat16, enabled=self.cuda):
             for i in range(0, n, chunk):
-                lg = self.model(self.vx[i:i + chunk]).float()
-                vl += float(F.cross_entropy(lg, self.vy[i:i + chunk], reduction="sum"))
-                vc += float((lg.argmax(1) == self.vy[i:i + chunk]).sum())
+                if self.vx is None:
+                    vi = torch.arange(i, min(i + chunk, n), device=self.dev)
+                    xv = self._nchw(augment_gather(self.vsrc, vi, PLAIN, self.lut, nhwc=True))
+                    yv = self.vy[i:i + vi.numel()]
+                else:
+                    xv, yv = self.vx[i:i + chunk], self.vy[i:i + chunk]
+                lg = self.model(xv).float()
+                vl += float(F.cross_entropy(lg, yv, reduction="sum"))
+                vc += float((lg.argmax(1) == yv).sum())
         self.model.train()
         return vl / max(n, 1), vc / max(n, 1)
 
@@ -273,13 +342,17 @@ def main(argv=None):
     arch = json.loads(_unquote(args.architecture).replace("'", '"'))
     nn_config = json.loads(_unquote(args.nn_config).replace("'", '"'))
     print(">>> arch received by trial\n%s" % arch, flush=True)
-    tr = ChildTrainer(arch, nn_config, args.num_train, args.num_valid, args.batch_size, bool(args.capture), args.seed)
+    augment = bool(args.data_dir) if args.augment == "auto" else args.augment == "1"
+    tr = ChildTrainer(arch, nn_config, args.num_train, args.num_valid, args.batch_size, bool(args.capture), args.seed,
+                      data_dir=args.data_dir, augment=augment)
     comm, dev, bs, steps = tr.comm, tr.dev, tr.bs, tr.steps
     gen = torch.Generator(device=dev).manual_seed(args.seed + comm.rank)
     timer = Timer()
     va = 0.0
     for epoch in range(args.num_epochs):
         tr.model.train()
+        if tr.epoch_t is not None:  # the device epoch of the augmentation draws, outside the captured step
+            tr.epoch_t.fill_(epoch)
         perm = torch.randperm(tr.shard, device=dev, generator=gen)[:steps * bs].view(steps, bs) + comm.rank * tr.shard
         tr.acc_buf.zero_()
         for s in range(steps):
