@@ -10,6 +10,15 @@ namespace {
 
 constexpr int kWave = 64;
 
+// The arithmetic of the spelled-out rounding orders below. hipcc defines __fmul_rn / __fadd_rn /
+// __fsub_rn as plain x * y, x + y, x - y, which it then contracts into FMAs (a rounding fewer
+// than documented); with contraction off inside these, every operation rounds on its own.
+#pragma clang fp contract(off)
+__device__ inline float mul_rn(float x, float y) { return x * y; }
+__device__ inline float add_rn(float x, float y) { return x + y; }
+__device__ inline float sub_rn(float x, float y) { return x - y; }
+#pragma clang fp contract(fast)
+
 __device__ inline double wave_sum(double v) {
 #pragma unroll
   for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
@@ -61,8 +70,8 @@ __global__ void __launch_bounds__(kThreads) virtual_step_kernel(VirtualStepArgs 
   for (int i = blockIdx.x * kThreads + threadIdx.x; i < a.n; i += stride) {
     const float w = a.w[i];
     // v = (mu * m + g) + wd * w;  w' = w + (-lr) * v   (architect.py:30-47 operation order)
-    const float v = __fadd_rn(__fadd_rn(__fmul_rn(a.mom[i], a.mu), a.g[i]), __fmul_rn(w, a.wd));
-    a.wv[i] = __fadd_rn(__fmul_rn(v, -lr), w);
+    const float v = add_rn(add_rn(mul_rn(a.mom[i], a.mu), a.g[i]), mul_rn(w, a.wd));
+    a.wv[i] = add_rn(mul_rn(v, -lr), w);
     if (a.g_zero) a.g_zero[i] = 0.0f;  // same thread, after its read of g[i]
   }
   for (int i = blockIdx.x * kThreads + threadIdx.x; i < a.n_zero_w; i += stride) a.zero_w[i] = 0.0f;
@@ -80,11 +89,11 @@ __global__ void __launch_bounds__(kThreads) hessian_kernel(HessianArgs a) {
   if (a.phase == 3) {  // concurrent form: both perturbed weight vectors at once, w untouched
     eps = __fdiv_rn(0.01f, static_cast<float>(sqrt(total_of(a.parts, a.nparts))));
     if (blockIdx.x == 0 && threadIdx.x == 0) *a.eps = eps;
-    const float m2 = -__fmul_rn(2.0f, eps);
+    const float m2 = -mul_rn(2.0f, eps);
     for (int i = i0; i < a.n; i += stride) {
-      const float wp = __fadd_rn(a.w[i], __fmul_rn(a.d[i], eps));
+      const float wp = add_rn(a.w[i], mul_rn(a.d[i], eps));
       a.wp[i] = wp;
-      a.wm[i] = __fadd_rn(wp, __fmul_rn(a.d[i], m2));
+      a.wm[i] = add_rn(wp, mul_rn(a.d[i], m2));
     }
     for (int i = i0; i < a.nbn; i += stride) {
       const float v = a.bn[i];
@@ -98,7 +107,7 @@ __global__ void __launch_bounds__(kThreads) hessian_kernel(HessianArgs a) {
   if (a.phase == 2 && a.nbn > 0) {
     const float k = 1.0f - a.bn_momentum;
     for (int i = i0; i < a.nbn; i += stride)
-      a.bn[i] = __fsub_rn(__fadd_rn(__fmul_rn(k, a.bn_plus[i]), a.bn[i]), __fmul_rn(k, a.bn_zero[i]));
+      a.bn[i] = sub_rn(add_rn(mul_rn(k, a.bn_plus[i]), a.bn[i]), mul_rn(k, a.bn_zero[i]));
   }
   if (a.phase == 0) {
     const float norm = static_cast<float>(sqrt(total_of(a.parts, a.nparts)));
@@ -107,9 +116,9 @@ __global__ void __launch_bounds__(kThreads) hessian_kernel(HessianArgs a) {
   } else {
     eps = *a.eps;
   }
-  const float scale = a.phase == 1 ? -__fmul_rn(2.0f, eps) : eps;
+  const float scale = a.phase == 1 ? -mul_rn(2.0f, eps) : eps;
   for (int i = blockIdx.x * kThreads + threadIdx.x; i < a.n; i += gridDim.x * kThreads)
-    a.w[i] = __fadd_rn(a.w[i], __fmul_rn(a.d[i], scale));
+    a.w[i] = add_rn(a.w[i], mul_rn(a.d[i], scale));
   if (blockIdx.x == 0) {
     if (a.phase == 0) {
       for (int i = threadIdx.x; i < a.na; i += kThreads) a.ga[i] = 0.0f;
@@ -119,10 +128,10 @@ __global__ void __launch_bounds__(kThreads) hessian_kernel(HessianArgs a) {
         a.ga[i] = 0.0f;
       }
     } else {
-      const float lr = *a.lr, two_eps = __fmul_rn(2.0f, eps);
+      const float lr = *a.lr, two_eps = mul_rn(2.0f, eps);
       for (int i = threadIdx.x; i < a.na; i += kThreads) {
-        const float h = __fdiv_rn(__fsub_rn(a.gap[i], a.ga[i]), two_eps);
-        a.alpha_grad[i] = __fsub_rn(a.gav[i], __fmul_rn(h, lr));
+        const float h = __fdiv_rn(sub_rn(a.gap[i], a.ga[i]), two_eps);
+        a.alpha_grad[i] = sub_rn(a.gav[i], mul_rn(h, lr));
       }
     }
   }
@@ -151,12 +160,12 @@ __global__ void __launch_bounds__(kThreads) sgd_clip_kernel(SgdArgs a) {
   const float coef = fminf(__fdiv_rn(a.clip, total + 1e-6f), 1.0f);
   const float lr = *a.lr;
   for (int i = blockIdx.x * kThreads + threadIdx.x; i < a.n; i += gridDim.x * kThreads) {
-    const float g = __fmul_rn(a.g[i], coef);
+    const float g = mul_rn(a.g[i], coef);
     const float w = a.w[i];
     a.g[i] = a.zero_g ? 0.0f : g;
-    const float m = __fadd_rn(__fmul_rn(a.mom[i], a.mu), __fadd_rn(g, __fmul_rn(w, a.wd)));
+    const float m = add_rn(mul_rn(a.mom[i], a.mu), add_rn(g, mul_rn(w, a.wd)));
     a.mom[i] = m;
-    a.w[i] = __fsub_rn(w, __fmul_rn(m, lr));
+    a.w[i] = sub_rn(w, mul_rn(m, lr));
   }
 }
 

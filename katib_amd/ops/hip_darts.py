@@ -1421,15 +1421,23 @@ class NetSpec:
         self.index = {n: i for i, n in enumerate(names)}
 
 
+ALPHA_GRAD_MAX = 128  # entries of one alpha_grad launch (kAlphaGradMax, csrc/hip/darts_optim.h)
+
+
 def _alpha_grad(entries):
     """alpha_grad launches over (g replicas, rstride, weight row, destination row) entries, each
-    destination row's entries in one launch (the kernel sums them per row, deterministically)."""
+    destination row's entries in one launch (the kernel sums them per row, deterministically).
+    Rows are packed up to 64 entries per launch; a row of its own may hold up to the kernel's
+    ALPHA_GRAD_MAX entries."""
     groups = defaultdict(list)
     for ent in entries:
         groups[ent[3].data_ptr()].append(ent)
     chunk = []
     for rows in groups.values():
-        if len(chunk) + len(rows) > 64:
+        if len(rows) > ALPHA_GRAD_MAX:
+            raise ValueError("alpha_grad: %d entries share one destination row, the kernel takes at most %d"
+                             % (len(rows), ALPHA_GRAD_MAX))
+        if chunk and len(chunk) + len(rows) > 64:
             _K.alpha_grad(chunk, True)
             chunk = []
         chunk += rows
