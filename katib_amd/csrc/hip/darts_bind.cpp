@@ -69,10 +69,6 @@ int64_t storage_doubles_after(const Tensor& t) {
   return (int64_t)(t.storage().nbytes() / sizeof(double)) - t.storage_offset();
 }
 
-int64_t gs_numel(const py::tuple& t) {
-  return t[1].cast<Tensor>().numel();  // z, the pre-BN output the gradient is evaluated on
-}
-
 GradSrc make_gs(const py::tuple& t, int C) {
   GradSrc g{};
   TORCH_CHECK(t.size() == 9, "grad-source tuple has 9 fields");
@@ -102,68 +98,6 @@ GradSrc make_gs(const py::tuple& t, int C) {
     }
   }
   return g;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Self-folding launches (darts_ops.h FoldTail): a per-device ring of zeroed arrival counters,
-// registered once from Python outside any graph capture (set_fold_counters); every launch that
-// produces replicated f64 sums takes the next counter. Off unless set_selffold(true) (the
-// Python side then launches fold_f64 as before; selffold_ready() tells it which mode is live).
-// ------------------------------------------------------------------------------------------------
-struct CtrRing {
-  unsigned* base = nullptr;
-  int size = 0;
-  int cursor = 0;
-};
-CtrRing g_ring[64];
-bool g_selffold = false;  // self-folding launches (set_selffold): measured slower, tests only
-
-void set_selffold(bool on) { g_selffold = on; }
-
-int cur_device() {
-  int d = 0;
-  TORCH_CHECK(hipGetDevice(&d) == hipSuccess, "hipGetDevice");
-  return d;
-}
-
-void set_fold_counters(Tensor t) {
-  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous() && t.numel() >= 4 * kFoldCtrSlot,
-              "fold counters: contiguous int32 GPU tensor of >= 4 launch slots");
-  const int d = t.get_device();
-  TORCH_CHECK(d >= 0 && d < 64, "device index");
-  g_ring[d] = CtrRing{reinterpret_cast<unsigned*>(t.data_ptr<int>()), (int)(t.numel() / kFoldCtrSlot), 0};
-}
-
-bool selffold_ready() { return g_selffold && g_ring[cur_device()].base != nullptr; }
-
-void tail_begin(FoldTail& t) {
-  t.nseg = 0;
-  t.ctr = nullptr;
-  if (!g_selffold) return;
-  CtrRing& r = g_ring[cur_device()];
-  if (!r.base) return;
-  t.ctr = r.base + (size_t)r.cursor * kFoldCtrSlot;  // size counts launch slots
-  r.cursor = (r.cursor + 1) % r.size;
-}
-
-void tail_add(FoldTail& t, double* p, int n, int rs) {
-  if (!t.ctr || !p) return;
-  for (int s = 0; s < t.nseg; ++s)
-    if (t.p[s] == p) {
-      t.n[s] = std::max(t.n[s], n);
-      return;
-    }
-  TORCH_CHECK(t.nseg < kTailSeg, "self-fold: too many reduction segments in one launch");
-  // (a launch with no segment keeps ctr == nullptr: see tail_close)
-  t.p[t.nseg] = p;
-  t.n[t.nseg] = n;
-  t.rs[t.nseg] = rs;
-  ++t.nseg;
-}
-
-// a launch that ended up with nothing to fold (eval mode: no statistics) skips the epilogue
-void tail_close(FoldTail& t) {
-  if (t.nseg == 0) t.ctr = nullptr;
 }
 
 int pick_chunk(int C, int per_channel_floats, int fixed_floats) {
@@ -238,24 +172,6 @@ static bool fill_dwpw(const py::tuple& t, DwPwFwdArgs& a, int64_t K, int64_t dil
   return prebn;
 }
 
-// (x, dw, pw, inbn|None, d, z, stats|None)
-void dwpw_fwd(std::vector<py::tuple> calls, int64_t K, int64_t dil, int64_t S, int64_t pad, bool use_mfma) {
-  check_batch<DwPwFwdBatch>(calls);
-  DwPwFwdBatch bt{};
-  bt.n = calls.size();
-  bool prebn = false;
-  for (int i = 0; i < bt.n; ++i) {
-    const bool pb = fill_dwpw(calls[i], bt.e[i], K, dil, S, pad, bt.n, use_mfma);
-    if (i == 0) prebn = pb;
-    TORCH_CHECK(pb == prebn, "edges in a batch must agree on the input BN");
-    SAME_SHAPE(bt, N); SAME_SHAPE(bt, C); SAME_SHAPE(bt, H); SAME_SHAPE(bt, W);
-  }
-  tail_begin(bt.tail);
-  for (int i = 0; i < bt.n; ++i) tail_add(bt.tail, bt.e[i].stats, 2 * bt.e[i].C, 2 * bt.e[i].C);
-  tail_close(bt.tail);
-  launch_dwpw_fwd(bt, K, dil, S, prebn, cur_stream());
-}
-
 // Mixed (K, dil, S, input-BN) entries of one node stage in one launch:
 // (x, dw, pw, inbn|None, d, z, stats|None, K, dil, S, pad) per entry. Entries that do not fit the
 // plane kernels (channel counts, alignment) run as per-group launches instead.
@@ -270,9 +186,6 @@ static void fill_dwpw_multi(const std::vector<py::tuple>& calls, DwPwMultiBatch&
     pre[i] = fill_dwpw(t, bt.e[i], kk[i], dd[i], ss[i], pp[i], bt.n, true);
     SAME_SHAPE(bt, N); SAME_SHAPE(bt, C); SAME_SHAPE(bt, Ho); SAME_SHAPE(bt, Wo);
   }
-  tail_begin(bt.tail);
-  for (int i = 0; i < bt.n; ++i) tail_add(bt.tail, bt.e[i].stats, 2 * bt.e[i].C, 2 * bt.e[i].C);
-  tail_close(bt.tail);
 }
 
 void dwpw_fwd_multi(std::vector<py::tuple> calls) {
@@ -284,7 +197,6 @@ void dwpw_fwd_multi(std::vector<py::tuple> calls) {
   for (int i = 0; i < bt.n; ++i) {  // fallback: one launch per entry (the plane path's band count is per batch)
     DwPwFwdBatch one{};
     one.n = 1;
-    one.tail = bt.tail;  // sequential launches may share the counter (each re-arms it)
     fill_dwpw(calls[i], one.e[0], kk[i], dd[i], ss[i], pp[i], 1, true);
     launch_dwpw_fwd(one, kk[i], dd[i], ss[i], pre[i], cur_stream());
   }
@@ -319,19 +231,18 @@ void pw_fwd(std::vector<py::tuple> calls, int64_t S) {
     a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.S = S; a.off = off; a.relu = 1; a.xnodes = xnodes;
     SAME_SHAPE(bt, N); SAME_SHAPE(bt, Cin); SAME_SHAPE(bt, Cout); SAME_SHAPE(bt, Ho); SAME_SHAPE(bt, Wo);
   }
-  tail_begin(bt.tail);
-  for (int i = 0; i < bt.n; ++i) tail_add(bt.tail, bt.e[i].stats, 2 * bt.e[i].CoutTotal, 2 * bt.e[i].CoutTotal);
-  tail_close(bt.tail);
   launch_pw_fwd(bt, cur_stream());
 }
 
-// (x, zavg, zmax, stats_avg|None, stats_max|None, amax|None[, S]); S < 0: per-entry S (7th field)
-static void fill_pool_fwd(const std::vector<py::tuple>& calls, int64_t S_all, PoolFwdBatch& bt) {
+// stride-1 and stride-2 pools of a node in one launch:
+// (x, zavg, zmax, stats_avg|None, stats_max|None, amax|None, S) per entry
+void pool_fwd_multi(std::vector<py::tuple> calls) {
   check_batch<PoolFwdBatch>(calls);
+  PoolFwdBatch bt{};
   bt.n = calls.size();
   for (int i = 0; i < bt.n; ++i) {
     const py::tuple& t = calls[i];
-    const int64_t S = S_all > 0 ? S_all : t[6].cast<int64_t>();
+    const int64_t S = t[6].cast<int64_t>();
     TORCH_CHECK(S == 1 || S == 2, "pool stride must be 1 or 2");
     bt.e[i].S = (int)S;
     Tensor x = t[0].cast<Tensor>(), zavg = t[1].cast<Tensor>(), zmax = t[2].cast<Tensor>();
@@ -349,39 +260,8 @@ static void fill_pool_fwd(const std::vector<py::tuple>& calls, int64_t S_all, Po
     a.N = x.size(0); a.C = x.size(1); a.H = x.size(2); a.W = x.size(3); a.Ho = zavg.size(2); a.Wo = zavg.size(3);
     TORCH_CHECK(a.Ho == (a.H - 1) / S + 1 && zmax.sizes() == zavg.sizes(), "pool shapes");
     SAME_SHAPE(bt, N); SAME_SHAPE(bt, C);
-    if (S_all > 0) { SAME_SHAPE(bt, H); SAME_SHAPE(bt, W); }
   }
-  tail_begin(bt.tail);
-  for (int i = 0; i < bt.n; ++i) {
-    tail_add(bt.tail, bt.e[i].stats_avg, 2 * bt.e[i].C, 2 * bt.e[i].C);
-    tail_add(bt.tail, bt.e[i].stats_max, 2 * bt.e[i].C, 2 * bt.e[i].C);
-  }
-  tail_close(bt.tail);
-}
-
-static void pool_fwd_impl(std::vector<py::tuple> calls, int64_t S_all) {
-  PoolFwdBatch bt{};
-  fill_pool_fwd(calls, S_all, bt);
-  if (S_all > 0) launch_pool_fwd(bt, S_all, cur_stream());
-  else launch_pool_fwd_multi(bt, cur_stream());
-}
-
-void pool_fwd(std::vector<py::tuple> calls, int64_t S) { pool_fwd_impl(calls, S); }
-// stride-1 and stride-2 pools of a node in one launch: (..., amax|None, S) per entry
-void pool_fwd_multi(std::vector<py::tuple> calls) { pool_fwd_impl(calls, -1); }
-
-// a node's stage-1 dw-pw entries and its pools (both read only the node inputs) in ONE launch
-// when the fused narrow-layer plane path applies; otherwise the two launches above
-void dwpw_pool_fwd_multi(std::vector<py::tuple> dcalls, std::vector<py::tuple> pcalls) {
-  DwPwMultiBatch bt{};
-  int64_t kk[DwPwMultiBatch::kCap], dd[DwPwMultiBatch::kCap], ss[DwPwMultiBatch::kCap], pp[DwPwMultiBatch::kCap];
-  bool pre[DwPwMultiBatch::kCap];
-  fill_dwpw_multi(dcalls, bt, kk, dd, ss, pp, pre);
-  PoolFwdBatch pb{};
-  fill_pool_fwd(pcalls, -1, pb);
-  if (launch_dwpw_pool_multi(bt, pb, cur_stream())) return;
-  dwpw_fwd_multi(dcalls);
-  launch_pool_fwd_multi(pb, cur_stream());
+  launch_pool_fwd_multi(bt, cur_stream());
 }
 
 // calls: per edge (zs, bns, widx, w|None, id_idx, xid|None, upd); all edges summed into `out`
@@ -471,12 +351,6 @@ void combine_bwd_reduce(std::vector<py::tuple> calls) {
     }
     SAME_SHAPE(bt, N); SAME_SHAPE(bt, C); SAME_SHAPE(bt, HW);
   }
-  tail_begin(bt.tail);
-  for (int i = 0; i < bt.n; ++i) {
-    tail_add(bt.tail, bt.e[i].red, bt.e[i].rstride, bt.e[i].rstride);
-    tail_add(bt.tail, bt.e[i].gw, bt.e[i].gwstride, bt.e[i].gwstride);
-  }
-  tail_close(bt.tail);
   launch_combine_bwd_reduce(bt, cur_stream());
 }
 
@@ -547,18 +421,6 @@ void pw_bwd(std::vector<py::tuple> calls, int64_t S, int64_t mode, bool need_dx)
 void dw_bwd_fill(std::vector<py::tuple>& calls, DwBwdBatch& bt, const int64_t* Ks, const int64_t* dils,
                  const int64_t* Ss, bool& prebn);
 
-void dw_bwd(std::vector<py::tuple> calls, int64_t K, int64_t dil, int64_t S, int64_t pad) {
-  check_batch<DwBwdBatch>(calls);
-  DwBwdBatch bt{};
-  int64_t Ks[DwBwdBatch::kCap], Ds[DwBwdBatch::kCap], Ss[DwBwdBatch::kCap];
-  for (int i = 0; i < DwBwdBatch::kCap; ++i) Ks[i] = K, Ds[i] = dil, Ss[i] = S;
-  TORCH_CHECK(pad == (K - 1) / 2 * dil, "dw_bwd padding must be 'same'");
-  bool prebn = false;
-  dw_bwd_fill(calls, bt, Ks, Ds, Ss, prebn);
-  tail_close(bt.tail);
-  launch_dw_bwd(bt, K, dil, S, prebn, cur_stream());
-}
-
 // Depthwise backward entries of mixed kernel size / dilation / stride that write DISTINCT outputs,
 // in one launch: (x, inbn, dw, dd, gout, gW|None, red|None, gstride, overwrite, K[, dil, S]) -
 // a node's separable second stages (input BN), or its stage-1 separable and dilated convolutions
@@ -586,11 +448,9 @@ void dw_bwd_multi(std::vector<py::tuple> calls) {
   }
   for (int i = 0; i < bt.n; ++i)  // no ordering between entries: distinct outputs
     for (int j = i + 1; j < bt.n; ++j) TORCH_CHECK(bt.e[i].gout != bt.e[j].gout, "dw_bwd_multi entries share an output");
-  tail_close(bt.tail);
   if (launch_dw_bwd_multi(bt, cur_stream())) return;
-  for (int v = 0; v < 16; ++v) {  // fallback: per variant, sharing the counter (sequential launches)
+  for (int v = 0; v < 16; ++v) {  // fallback: per variant
     DwBwdBatch one{};
-    one.tail = bt.tail;
     for (int i = 0; i < bt.n; ++i)
       if (bt.e[i].variant == v) one.e[one.n++] = bt.e[i];
     if (one.n) launch_dw_bwd(one, dw_variant_k(v), dw_variant_dil(v), dw_variant_s(v), prebn, cur_stream());
@@ -642,19 +502,17 @@ void dw_bwd_fill(std::vector<py::tuple>& calls, DwBwdBatch& bt, const int64_t* K
     if (prebn) a.inbn = make_bn(*inbn, a.C);
     SAME_SHAPE(bt, N); SAME_SHAPE(bt, C); SAME_SHAPE(bt, Ho); SAME_SHAPE(bt, Wo);
   }
-  tail_begin(bt.tail);
-  if (prebn)
-    for (int i = 0; i < bt.n; ++i) tail_add(bt.tail, bt.e[i].red, 2 * bt.e[i].C, 2 * bt.e[i].C);
 }
 
-// (ga|None, gm|None, x, dout_id|None, w|None, id_idx, gx, amax|None, overwrite[, S]); S < 0: per entry
-static void pool_bwd_impl(std::vector<py::tuple> calls, int64_t S_all) {
+// stride-1 and stride-2 pool backward of a node in one launch:
+// (ga|None, gm|None, x, dout_id|None, w|None, id_idx, gx, amax|None, overwrite, S[, extras]) per entry
+void pool_bwd_multi(std::vector<py::tuple> calls) {
   check_batch<PoolBwdBatch>(calls);
   PoolBwdBatch bt{};
   bt.n = calls.size();
   for (int i = 0; i < bt.n; ++i) {
     const py::tuple& t = calls[i];
-    const int64_t S = S_all > 0 ? S_all : t[9].cast<int64_t>();
+    const int64_t S = t[9].cast<int64_t>();
     TORCH_CHECK(S == 1 || S == 2, "pool stride must be 1 or 2");
     bt.e[i].S = (int)S;
     auto ga = t[0].cast<c10::optional<py::tuple>>(), gm = t[1].cast<c10::optional<py::tuple>>();
@@ -679,7 +537,7 @@ static void pool_bwd_impl(std::vector<py::tuple> calls, int64_t S_all) {
     if (a.dout_id) TORCH_CHECK(dout_id->sizes() == x.sizes(), "identity gradient shape");
     a.id_idx = id_idx; a.gx = gx.data_ptr<float>();
     a.overwrite = t[8].cast<bool>();
-    if (S_all <= 0 && t.size() > 10) {  // (..., S, extras): other input-gradient parts to sum in
+    if (t.size() > 10) {  // (..., S, extras): other input-gradient parts to sum in
       auto ex = t[10].cast<std::vector<Tensor>>();
       TORCH_CHECK(ex.size() <= 4, "pool_bwd: at most 4 extra gradient parts");
       a.nextra = ex.size();
@@ -691,81 +549,12 @@ static void pool_bwd_impl(std::vector<py::tuple> calls, int64_t S_all) {
       }
     }
     SAME_SHAPE(bt, N); SAME_SHAPE(bt, C);
-    if (S_all > 0) { SAME_SHAPE(bt, H); SAME_SHAPE(bt, W); }
   }
   // entries of one launch must write distinct input gradients (no ordering between them)
   for (int i = 0; i < bt.n; ++i)
     for (int j = i + 1; j < bt.n; ++j) TORCH_CHECK(bt.e[i].gx != bt.e[j].gx, "pool_bwd entries share a gx buffer");
-  if (S_all > 0) launch_pool_bwd(bt, S_all, cur_stream());
-  else launch_pool_bwd_multi(bt, cur_stream());
+  launch_pool_bwd_multi(bt, cur_stream());
 }
-
-void pool_bwd(std::vector<py::tuple> calls, int64_t S) { pool_bwd_impl(calls, S); }
-
-// Whole input gradient of up to 4 edges of one node (distinct gx buffers), one launch:
-// per edge (x, gx, overwrite, convs, ga|None, gm|None, amax|None, dout_id|None, w|None, id_idx, S);
-// convs = 4 slots (sep 3x3, sep 5x5, dil 3x3, dil 5x5), each None or (dw, dd, gW|None, gstride).
-// Returns false (nothing launched) when the shapes fall outside the fused kernel.
-bool edge_bwd(std::vector<py::tuple> calls) {
-  check_batch<EdgeBwdBatch>(calls);
-  EdgeBwdBatch bt{};
-  bt.n = calls.size();
-  const int Ks[4] = {3, 5, 3, 5};
-  for (int i = 0; i < bt.n; ++i) {
-    const py::tuple& t = calls[i];
-    TORCH_CHECK(t.size() == 11, "edge_bwd entry: (x, gx, overwrite, convs, ga, gm, amax, dout_id, w, id_idx, S)");
-    Tensor x = t[0].cast<Tensor>(), gx = t[1].cast<Tensor>();
-    check_f32(x, "x"); check_f32(gx, "gx");
-    TORCH_CHECK(x.dim() == 4 && gx.sizes() == x.sizes(), "gx shape");
-    EdgeBwdArgs& a = bt.e[i];
-    a.x = x.data_ptr<float>(); a.gx = gx.data_ptr<float>(); a.overwrite = t[2].cast<bool>();
-    a.S = t[10].cast<int>();
-    TORCH_CHECK(a.S == 1 || a.S == 2, "stride");
-    a.N = x.size(0); a.C = x.size(1); a.H = x.size(2); a.W = x.size(3);
-    a.Ho = (a.H - 1) / a.S + 1; a.Wo = (a.W - 1) / a.S + 1;
-    auto convs = t[3].cast<std::vector<py::object>>();
-    TORCH_CHECK(convs.size() == 4, "4 conv slots");
-    for (int v = 0; v < 4; ++v) {
-      if (convs[v].is_none()) continue;
-      py::tuple c = convs[v].cast<py::tuple>();
-      Tensor dw = c[0].cast<Tensor>(), dd = c[1].cast<Tensor>();
-      OptT gW = c[2].cast<OptT>();
-      const int64_t gstride = c[3].cast<int64_t>();
-      check_f32(dw, "dw"); check_f32(dd, "dd");
-      TORCH_CHECK(dw.numel() == a.C * Ks[v] * Ks[v], "dw shape");
-      TORCH_CHECK(dd.dim() == 4 && dd.size(0) == a.N && dd.size(1) == a.C && dd.size(2) == a.Ho && dd.size(3) == a.Wo,
-                  "dd shape");
-      check_grad_sink(gW, (int64_t)a.C * Ks[v] * Ks[v], gstride);
-      a.dw[v] = dw.data_ptr<float>(); a.dd[v] = dd.data_ptr<float>(); a.gW[v] = ptr_or_null<float>(gW);
-      a.gstride[v] = gstride;
-      a.conv_mask |= 1 << v;
-    }
-    auto ga = t[4].cast<c10::optional<py::tuple>>(), gm = t[5].cast<c10::optional<py::tuple>>();
-    OptT amax = t[6].cast<OptT>(), dout_id = t[7].cast<OptT>(), w = t[8].cast<OptT>();
-    if (ga.has_value()) {
-      a.ga = make_gs(*ga, a.C);
-      TORCH_CHECK(gs_numel(*ga) == (int64_t)a.N * a.C * a.Ho * a.Wo, "avg-pool gradient source shape");
-    }
-    if (gm.has_value()) {
-      a.gm = make_gs(*gm, a.C);
-      TORCH_CHECK(gs_numel(*gm) == (int64_t)a.N * a.C * a.Ho * a.Wo, "max-pool gradient source shape");
-      TORCH_CHECK(amax.has_value() && amax->defined() && amax->scalar_type() == at::kByte &&
-                      amax->numel() == (int64_t)a.N * a.C * a.Ho * a.Wo,
-                  "max-pool backward needs the uint8 argmax from pool_fwd");
-      a.amax = amax->data_ptr<uint8_t>();
-    }
-    a.dout_id = ptr_or_null<float>(dout_id); a.w = ptr_or_null<float>(w); a.id_idx = t[9].cast<int>();
-    if (a.dout_id) {
-      check_f32(*dout_id, "dout_id");
-      TORCH_CHECK(dout_id->sizes() == x.sizes() && a.S == 1, "identity gradient shape");
-    }
-    SAME_SHAPE(bt, N); SAME_SHAPE(bt, C);
-  }
-  for (int i = 0; i < bt.n; ++i)
-    for (int j = i + 1; j < bt.n; ++j) TORCH_CHECK(bt.e[i].gx != bt.e[j].gx, "edge_bwd entries share a gx buffer");
-  return launch_edge_bwd(bt, cur_stream());
-}
-void pool_bwd_multi(std::vector<py::tuple> calls) { pool_bwd_impl(calls, -1); }
 
 void fold_rows(Tensor buf) {
   check_f32(buf, "buf");
@@ -812,20 +601,14 @@ void register_augment(py::module& m);  // augment_bind.cpp
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "katib_amd HIP kernels for gfx950 (DARTS edge ops, implicit-GEMM conv, transformer, xGMI all-reduce)";
-  m.def("dwpw_fwd", &dwpw_fwd);
   m.def("pw_fwd", &pw_fwd);
-  m.def("pool_fwd", &pool_fwd);
   m.def("combine_fwd", &combine_fwd);
   m.def("combine_bwd_reduce", &combine_bwd_reduce);
   m.def("pw_bwd", &pw_bwd);
-  m.def("dw_bwd", &dw_bwd);
   m.def("dw_bwd_multi", &dw_bwd_multi, "separable second-stage depthwise backward of mixed kernel size in one launch");
-  m.def("pool_bwd", &pool_bwd);
   m.def("dwpw_fwd_multi", &dwpw_fwd_multi, "mixed (K, dil, S) dw-pw entries of one node stage in one launch");
   m.def("pool_fwd_multi", &pool_fwd_multi, "stride-1 and stride-2 pools in one launch");
-  m.def("dwpw_pool_fwd_multi", &dwpw_pool_fwd_multi, "a node's stage-1 dw-pw entries and its pools in one launch");
   m.def("pool_bwd_multi", &pool_bwd_multi, "stride-1 and stride-2 pool backward in one launch");
-  m.def("edge_bwd", &edge_bwd, "whole input gradient of a node's edges (convs, pools, identity) in one launch");
   m.def("set_max_blocks", &set_max_blocks);
   m.def("stamps_arm", [](int kind, int call, torch::Tensor buf) {
     TORCH_CHECK(!buf.defined() || kind == 0 || (buf.is_cuda() && buf.scalar_type() == torch::kInt64 &&
@@ -836,9 +619,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("stamps_compiled", &stamps_compiled);
   m.def("fold_rows", &fold_rows);
   m.def("fold_f64", &fold_f64);
-  m.def("set_fold_counters", &set_fold_counters, "register the current device's self-fold counter ring (int32, zeroed)");
-  m.def("selffold_ready", &selffold_ready, "launches on the current device fold their own f64 replicas");
-  m.def("set_selffold", &set_selffold, "turn self-folding launches on / off (default off: measured slower)");
   m.attr("REP") = kRep;
   m.attr("ZBF16") = kZbf16;  // per-op intermediates stored as bf16 (the _hipkern_zbf16 variant)
   m.def("max_blocks", &max_blocks);

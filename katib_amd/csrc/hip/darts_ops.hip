@@ -309,7 +309,6 @@ __global__ void __launch_bounds__(256) combine_bwd_reduce_kernel(CombineBwdBatch
       if (gw) atomicAdd(gw + a.widx[j - 2], (double)t);
     }
   }
-  if (bt.tail.ctr) fold_tail(bt.tail);
 }
 
 void launch_combine_fwd(const CombineFwdBatch& b, hipStream_t st) {

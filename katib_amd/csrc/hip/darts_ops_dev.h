@@ -359,53 +359,6 @@ __device__ __forceinline__ float4 xval4(const void* p, size_t i) {
   }
 }
 
-// Self-fold epilogue (darts_ops.h FoldTail). Called by EVERY thread of EVERY workgroup of the
-// launch, after the workgroup's last replica atomic. The arrival add is relaxed: the payload is
-// device-scope atomics (performed memory-side), drained by each wave's vmcnt(0) before the
-// workgroup barrier, and the folding workgroup reads it back with returning atomics only, so no
-// release / acquire fence (an XCD L2 write-back per workgroup) is needed.
-__device__ __forceinline__ void fold_tail(const FoldTail& t) {
-  __shared__ int s_last;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    // two-level arrival: same-address atomics serialise memory-side (~12 ns each), so ~2000
-    // workgroups on one counter cost ~25 us; kFoldShards shard counters (own 128-B lines) cut
-    // the chain to total / kFoldShards, and each shard's last arriver adds to the top counter
-    const unsigned total = gridDim.x * gridDim.y * gridDim.z;
-    const unsigned L = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    const unsigned sh = L % kFoldShards;
-    const unsigned cnt = total / kFoldShards + (sh < total % kFoldShards ? 1u : 0u);
-    unsigned* cs = t.ctr + (1 + sh) * kFoldCtrStride;
-    int last = 0;
-    if (__hip_atomic_fetch_add(cs, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == cnt - 1) {
-      __hip_atomic_store(cs, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm the shard
-      const unsigned nsh = total < (unsigned)kFoldShards ? total : (unsigned)kFoldShards;
-      last = __hip_atomic_fetch_add(t.ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nsh - 1;
-    }
-    s_last = last;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  int tot = 0;
-  for (int s = 0; s < t.nseg; ++s) tot += t.n[s];
-  for (int g = threadIdx.x; g < tot; g += blockDim.x) {
-    int s = 0, i = g;
-    while (i >= t.n[s]) i -= t.n[s++];
-    double* p = t.p[s] + i;
-    const size_t rs = t.rs[s];
-    double v[kRep - 1];
-#pragma unroll
-    for (int r = 1; r < kRep; ++r)  // all exchanges in flight together
-      v[r - 1] = __hip_atomic_exchange(p + r * rs, 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    double acc = 0.0;
-#pragma unroll
-    for (int r = 0; r < kRep - 1; ++r) acc += v[r];
-    __hip_atomic_fetch_add(p, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  if (threadIdx.x == 0) __hip_atomic_store(t.ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // ------------------------------------------------------------------------------------------------
 // pw_fwd_wave: z[:, co_off + co] = pw . act(x) for Cin, Cout multiples of 16 (<= 64), plus the BN
 // statistics of z. act = relu at (oy*S + off, ox*S + off) (StdConv / FactorizedReduce half) or the

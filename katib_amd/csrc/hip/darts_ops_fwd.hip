@@ -63,7 +63,6 @@ static bool try_dwpw_split_g(const DwPwFwdBatch& b, bool prebn, hipStream_t st, 
   };
   while (band_bytes(nb) > 65536 && nb < a.Ho) ++nb;
   DwPwFwdBatch db = b;
-  db.tail.ctr = nullptr;  // the statistics come from the pointwise launch below, which folds them
   for (int i = 0; i < b.n; ++i) db.e[i].chunk = nb;
   dim3 grid(a.N * nb * G, b.n);
   const size_t lds = band_bytes(nb);
@@ -71,7 +70,6 @@ static bool try_dwpw_split_g(const DwPwFwdBatch& b, bool prebn, hipStream_t st, 
   else hipLaunchKernelGGL((dwpw_plane_kernel<K, DIL, S, false, CG, true, false>), grid, dim3(256), lds, st, db);
   PwFwdBatch pb{};
   pb.n = b.n;
-  pb.tail = b.tail;
   for (int i = 0; i < b.n; ++i) {
     const DwPwFwdArgs& e = b.e[i];
     PwFwdArgs& p = pb.e[i];
@@ -168,15 +166,10 @@ bool launch_dwpw_multi(DwPwMultiBatch b, hipStream_t st) {
     else launch_dwpw_plane_multi_t<16>(true, grid, lds, st, b);
     return true;
   }
-  {
-    DwPwMultiBatch db = b;
-    db.tail.ctr = nullptr;  // statistics (and their fold) come from the pointwise launch
-    launch_dwpw_plane_multi_t<8>(false, grid, lds, st, db);
-  }
+  launch_dwpw_plane_multi_t<8>(false, grid, lds, st, b);  // the statistics come from the pointwise launch
   // the pointwise halves + BN statistics of every entry: one MFMA wave launch
   PwFwdBatch pb{};
   pb.n = b.n;
-  pb.tail = b.tail;  // per-entry launches below share the counter: they run one after another
   for (int i = 0; i < b.n; ++i) {
     const DwPwFwdArgs& e = b.e[i];
     PwFwdArgs& p = pb.e[i];
@@ -191,7 +184,6 @@ bool launch_dwpw_multi(DwPwMultiBatch b, hipStream_t st) {
   for (int i = 0; i < b.n; ++i) {  // mixed output sizes (stride-1 and stride-2 entries): per entry
     PwFwdBatch one{};
     one.n = 1;
-    one.tail = pb.tail;
     one.e[0] = pb.e[i];
     if (!(try_pw_fwd_wave<16, 16>(one, st) || try_pw_fwd_wave<32, 32>(one, st) || try_pw_fwd_wave<64, 64>(one, st)))
       launch_pw_fwd(one, st);
@@ -224,27 +216,6 @@ void launch_pool_fwd_multi(PoolFwdBatch b, hipStream_t st) {
   if (pool_fwd_prep(b.e, b.n, maxblk, lds))
     hipLaunchKernelGGL(pool_fwd_multi_kernel<true>, dim3(maxblk, b.n), dim3(256), lds, st, b);
   else hipLaunchKernelGGL(pool_fwd_multi_kernel<false>, dim3(maxblk, b.n), dim3(256), 0, st, b);
-}
-
-bool launch_dwpw_pool_multi(DwPwMultiBatch b, const PoolFwdBatch& pb, hipStream_t st) {
-  constexpr bool off = false;
-  if (off || b.n < 1 || pb.n < 1 || b.tail.ctr || pb.tail.ctr || b.n + pb.n > 65535) return false;
-  const int C = b.e[0].C;
-  bool fused;
-  int maxblk;
-  size_t lds;
-  if (!dwpw_multi_prep(b, fused, maxblk, lds) || !fused || (C != 4 && C != 8)) return false;
-  PoolFwdEntries pe{};
-  pe.n = pb.n;
-  for (int i = 0; i < pb.n; ++i) pe.e[i] = pb.e[i];
-  int pblk;
-  size_t plds;
-  if (!pool_fwd_prep(pe.e, pe.n, pblk, plds)) return false;  // the joint kernel carries the 4-pixel pool only
-  const dim3 grid(std::max(maxblk, pblk), b.n + pb.n);
-  lds = std::max(lds, plds);
-  if (C == 4) launch_dwpw_pool_t<4>(grid, lds, st, b, pe);
-  else launch_dwpw_pool_t<8>(grid, lds, st, b, pe);
-  return true;
 }
 
 template <int CI, int CO>
@@ -283,13 +254,6 @@ void launch_pw_fwd(const PwFwdBatch& b, hipStream_t st) {
   size_t lds = sizeof(float) * (a.Cin * 64 + 2 * a.Cout);
   dim3 grid(per_edge_blocks(a.N * a.Ho * a.Wo / 64, b.n), b.n);
   hipLaunchKernelGGL(pw_fwd_kernel, grid, dim3(256), lds, st, b);
-}
-
-void launch_pool_fwd(const PoolFwdBatch& b, int S, hipStream_t st) {
-  const PoolFwdArgs& a = b.e[0];
-  dim3 grid(a.C * channel_groups(a.N, a.C, b.n), b.n);
-  if (S == 1) hipLaunchKernelGGL(pool_fwd_kernel<1>, grid, dim3(256), 0, st, b);
-  else hipLaunchKernelGGL(pool_fwd_kernel<2>, grid, dim3(256), 0, st, b);
 }
 
 }  // namespace katib_hip

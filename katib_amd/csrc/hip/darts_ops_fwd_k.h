@@ -1,5 +1,5 @@
 // Internal: the DARTS forward kernel templates, included by darts_ops_fwd.hip (launchers, single-variant
-// instantiations) and darts_ops_fwd_m{4,8,16}.hip (the mixed-variant multi / joint kernels of one channel
+// instantiations) and darts_ops_fwd_m{4,8,16}.hip (the mixed-variant multi kernels of one channel
 // count each, so the heaviest instantiations compile in parallel).
 #pragma once
 #include "darts_ops_dev.h"
@@ -128,7 +128,6 @@ __global__ void __launch_bounds__(256) dwpw_fwd_kernel(DwPwFwdBatch bt) {
   }
   if (a.stats)  // one contiguous f64 atomic vector per block
     for (int i = tid; i < 2 * C; i += 256) atomicAdd(a.stats + rep_slot() * 2 * C + i, (double)sStat[i]);
-  if (bt.tail.ctr) fold_tail(bt.tail);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -348,7 +347,6 @@ __device__ __forceinline__ void dwpw_plane_body(const DwPwFwdArgs& a, const int 
 template <int K, int DIL, int S, bool PREBN, int C, bool VEC, bool PW = true>
 __global__ void __launch_bounds__(256) dwpw_plane_kernel(DwPwFwdBatch bt) {
   dwpw_plane_body<K, DIL, S, PREBN, C, VEC, PW>(bt.e[blockIdx.y], blockIdx.x);
-  if (bt.tail.ctr) fold_tail(bt.tail);
 }
 
 // One launch for a node's whole separable-stage / dilated-conv forward: every entry (edge x
@@ -374,7 +372,6 @@ __global__ void __launch_bounds__(256) dwpw_plane_multi_kernel(DwPwMultiBatch bt
       default: break;
     }
   }
-  if (bt.tail.ctr) fold_tail(bt.tail);
 }
 
 
@@ -477,7 +474,6 @@ __global__ void __launch_bounds__(256) pw_fwd_wave_kernel(PwFwdBatch bt) {
     atomicAdd(a.stats + rep_slot() * 2 * a.CoutTotal + hi * a.CoutTotal + a.co_off + (i - hi * CO), (double)sStat[i]);
   }
   }
-  if (bt.tail.ctr) fold_tail(bt.tail);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -532,7 +528,6 @@ static __global__ void __launch_bounds__(256) pw_fwd_kernel(PwFwdBatch bt) {
       atomicAdd(a.stats + rep_slot() * 2 * a.CoutTotal + hi * a.CoutTotal + a.co_off + (i - hi * Cout),
                 (double)sStat[i]);
     }
-  if (bt.tail.ctr) fold_tail(bt.tail);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -665,11 +660,6 @@ __device__ __forceinline__ void pool_fwd_body(const PoolFwdArgs& a, const int bx
     if (dst) atomicAdd(dst + (bx % kRep) * 2 * C + (threadIdx.x & 1) * C + c, (double)t);
   }
 }
-template <int S>
-__global__ void __launch_bounds__(256) pool_fwd_kernel(PoolFwdBatch bt) {
-  pool_fwd_body<S>(bt.e[blockIdx.y], blockIdx.x, gridDim.x);
-  if (bt.tail.ctr) fold_tail(bt.tail);
-}
 
 // stride-1 and stride-2 pooling of a node in one launch (entry a.S; a.nblk workgroups, a multiple of C)
 template <bool V4>
@@ -679,52 +669,19 @@ __global__ void __launch_bounds__(256) pool_fwd_multi_kernel(PoolFwdBatch bt) {
     if (a.S == 1) pool_fwd_body<1, V4>(a, blockIdx.x, a.nblk);
     else pool_fwd_body<2, V4>(a, blockIdx.x, a.nblk);
   }
-  if (bt.tail.ctr) fold_tail(bt.tail);
 }
 
-
-// A node's stage-1 depthwise-pointwise entries and its pools in ONE launch (both read only the
-// node's inputs): blockIdx.y < bt.n runs a dw-pw entry, the rest a pool entry, so the pool
-// workgroups fill the chip beside the dw-pw bands instead of running as a launch of their own
-// after them (fused narrow layers, no self-fold tails).
-template <int C, bool PV4>
-__global__ void __launch_bounds__(256) dwpw_pool_multi_kernel(DwPwMultiBatch bt, PoolFwdEntries pe) {
-  constexpr bool PW = true;
-  const int bx = blockIdx.x;
-  if ((int)blockIdx.y < bt.n) {
-    const DwPwFwdArgs a = bt.e[blockIdx.y];  // copy: see dwpw_plane_multi_kernel
-    if (bx < a.nblk) {
-      switch (a.variant) {
-        DWPW_CASE(3, 1, 1) DWPW_CASE(3, 1, 2) DWPW_CASE(5, 1, 1) DWPW_CASE(5, 1, 2)
-        DWPW_CASE(3, 2, 1) DWPW_CASE(3, 2, 2) DWPW_CASE(5, 2, 1) DWPW_CASE(5, 2, 2)
-        default: break;
-      }
-    }
-  } else {
-    const PoolFwdArgs a = pe.e[blockIdx.y - bt.n];
-    if (bx < a.nblk) {
-      if (a.S == 1) pool_fwd_body<1, PV4>(a, bx, a.nblk);
-      else pool_fwd_body<2, PV4>(a, bx, a.nblk);
-    }
-  }
-}
 #undef DWPW_CASE
 
 
 // per-channel-count launchers of the mixed-variant kernels (explicitly instantiated in darts_ops_fwd_m<C>.hip)
 template <int C>
 void launch_dwpw_plane_multi_t(bool pw, dim3 grid, size_t lds, hipStream_t st, const DwPwMultiBatch& b);
-template <int C>
-void launch_dwpw_pool_t(dim3 grid, size_t lds, hipStream_t st, const DwPwMultiBatch& b, const PoolFwdEntries& pe);
 template <>
 void launch_dwpw_plane_multi_t<4>(bool pw, dim3 grid, size_t lds, hipStream_t st, const DwPwMultiBatch& b);
 template <>
 void launch_dwpw_plane_multi_t<8>(bool pw, dim3 grid, size_t lds, hipStream_t st, const DwPwMultiBatch& b);
 template <>
 void launch_dwpw_plane_multi_t<16>(bool pw, dim3 grid, size_t lds, hipStream_t st, const DwPwMultiBatch& b);
-template <>
-void launch_dwpw_pool_t<4>(dim3 grid, size_t lds, hipStream_t st, const DwPwMultiBatch& b, const PoolFwdEntries& pe);
-template <>
-void launch_dwpw_pool_t<8>(dim3 grid, size_t lds, hipStream_t st, const DwPwMultiBatch& b, const PoolFwdEntries& pe);
 
 }  // namespace katib_hip

@@ -1,4 +1,4 @@
-// Mixed-variant dw-pw (and joint dw-pw + pool) kernels for C = 16 channel groups: one translation
+// Mixed-variant dw-pw kernels for C = 16 channel groups: one translation
 // unit per channel count so their 32-variant bodies compile in parallel.
 #include "darts_ops_fwd_k.h"
 

@@ -6,12 +6,12 @@ MixedOp ``sum_k softmax(alpha)_k * op_k(x_j)`` (reference
 ``model.py:61-71``) - with every kernel launched once for *all* edges of the node that
 share its shape (edge batches, ``blockIdx.y`` = edge):
 
-forward   dwpw_fwd per (kernel size, dilation, stride) [separable stage 1, dilated],
-          pool_fwd (avg + max + argmax), pw_fwd x2 (stride-2 skip = FactorizedReduce),
-          fold, dwpw_fwd with BN-apply prologue [separable stage 2], fold,
+forward   dwpw_fwd_multi over every (kernel size, dilation, stride) [separable stage 1, dilated],
+          pool_fwd_multi (avg + max + argmax), pw_fwd x2 (stride-2 skip = FactorizedReduce),
+          fold, dwpw_fwd_multi with BN-apply prologue [separable stage 2], fold,
           combine_fwd summing every edge's weighted BN outputs into the node (+ running stats)
 backward  combine_bwd_reduce (BN-backward sums + d softmax-weights), fold, then pw_bwd /
-          dw_bwd / pool_bwd batches; every input gradient is written (not accumulated) by
+          dw_bwd_multi / pool_bwd_multi batches; every input gradient is written (not accumulated) by
           its first kernel, so no memsets
 
 Cross-workgroup sums go to ``REP`` replicas of each accumulator (workgroup b adds
@@ -55,48 +55,6 @@ REP = int(_K.REP)
 # _hipkern_zbf16 build variant (KATIB_AMD_HIPKERN), fp32 otherwise; node states, gradients, BN
 # statistics and weights stay fp32 either way
 ZDT = torch.bfloat16 if bool(getattr(_K, "ZBF16", False)) else torch.float32
-# FOLD (module attribute, tests only): a fold_f64 launch sums the REP replicas of each cross-workgroup
-# reduction before its consumers (which then read rep=1); False: consumers sum the replicas themselves
-# and the fold launches disappear. Measured on MI355X (B5 step): 13.3 ms
-# with the folds, 17.1 ms without - every consumer workgroup re-reading 32 replicas costs more
-# than ~180 small fold launches.
-FOLD = True
-_R = 1 if FOLD else REP
-# Self-folding producers (darts_ops.h FoldTail): with a counter ring registered for the device,
-# every launch that adds into f64 replicas folds them in its last workgroup, and the fold_f64
-# launches between producers and consumers disappear. Needs FOLD (consumers read replica 0).
-# Off (set_selffold(True): tests and experiments): measured on MI355X, one arrival counter
-# made every producer ~15-25 us slower (2000 same-address atomics serialise memory-side: B5
-# step 12.1 ms), 32 sharded counters still lose to the fold launches (8.22 vs 8.05 ms),
-# profiles/darts_selffold_edge_ab_r03.log.
-SELFFOLD = False
-_CTR: Dict[int, torch.Tensor] = {}
-
-
-def set_selffold(on: bool):
-    """A/B switch for tests and experiments (call between steps, never inside a capture)."""
-    global SELFFOLD
-    if on and _SYNC is not None:
-        raise RuntimeError("self-folding producers cannot run under SyncBN (see _check_sync_fold_mode)")
-    SELFFOLD = bool(on)
-    _K.set_selffold(SELFFOLD)
-_CTR_SIZE = 64 * 33 * 32  # 64 launch slots of (top + 32 shard) counters, 128 B apart
-
-
-def _selffold(dev) -> bool:
-    """Register the device's counter ring on first use (never inside a graph capture, whose
-    private pool must not own it) and report whether producers on the current device fold
-    their own replicas (the C++ side attaches tails under exactly this condition)."""
-    if not FOLD or not SELFFOLD:
-        return False
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    if idx not in _CTR:
-        if torch.cuda.is_current_stream_capturing():
-            return bool(_K.selffold_ready())
-        t = torch.zeros(_CTR_SIZE, dtype=torch.int32, device=torch.device("cuda", idx))
-        _K.set_fold_counters(t)
-        _CTR[idx] = t
-    return bool(_K.selffold_ready())
 
 
 # SyncBN state of the step being built / run (set by DartsSearch through :func:`sync_scope`): BN
@@ -104,20 +62,6 @@ def _selffold(dev) -> bool:
 # fold_sync kernel of parallel/xgmi.py), so every rank normalises with the global batch's
 # statistics; None: per-rank BN
 _SYNC = None
-
-
-def _check_sync_fold_mode():
-    """SyncBN sums the BN reductions over the ranks inside the fold (``_fold`` / ``SyncBN.fold``)
-    and ``_bn`` then divides by count * world. Without fold launches (FOLD False) or with
-    self-folding producers (SELFFOLD True) that fold never runs, and every rank would
-    normalise its LOCAL sums by the global count - mean and variance off by a factor of world,
-    silently. Refuse those combinations."""
-    if not FOLD:
-        raise RuntimeError("SyncBN needs the fold launches (hip_darts.FOLD): the cross-rank BN sum "
-                           "happens inside them")
-    if SELFFOLD:
-        raise RuntimeError("SyncBN is incompatible with self-folding producers (hip_darts.SELFFOLD): "
-                           "their replicas would never be summed over the ranks")
 
 
 class SyncBN:
@@ -132,7 +76,6 @@ class SyncBN:
     passed ``Comm.probe_rccl_capture`` (else: host-side RCCL / gloo, step not captured)."""
 
     def __init__(self, comm):
-        _check_sync_fold_mode()
         self.comm, self.world = comm, comm.world_size
         self.ws = None
         if comm.xgmi is not None:
@@ -170,8 +113,6 @@ class sync_scope:
 
     def __enter__(self):
         global _SYNC
-        if self.sync is not None:
-            _check_sync_fold_mode()
         self.prev, _SYNC = _SYNC, self.sync
         return self
 
@@ -196,18 +137,14 @@ def _fold(segs):
         _K.fold_f64([tuple(sg[:3]) for sg in segs])
 
 
-def _defer(dev) -> bool:
+def _defer() -> bool:
     """Consumers may sum the replicas themselves (deferred folds; never under SyncBN, whose
     cross-rank sum happens in the fold)."""
-    return DEFER_FOLD and FOLD and _SYNC is None and not _selffold(dev)
+    return _SYNC is None
 
 
-def _fold64(segs, dev=None):
-    """fold_f64 launch between producers and consumers, unless the producers folded themselves."""
-    if FOLD and (dev is None or not _selffold(dev)):
-        _fold(segs)
-_CAP = {"combine_fwd": 4, "dwpw_fwd": 8, "pw_fwd": 16, "pool_fwd": 8, "combine_bwd_reduce": 4, "pw_bwd": 16,
-        "dw_bwd": 20, "pool_bwd": 8}
+_CAP = {"combine_fwd": 4, "dwpw_fwd_multi": 20, "pw_fwd": 16, "pool_fwd_multi": 8, "combine_bwd_reduce": 4,
+        "pw_bwd": 16, "dw_bwd_multi": 20, "pool_bwd_multi": 8}
 _REPLICATED: List[Tuple[weakref.ref, int]] = []  # (buffer [REP][n], n)
 
 
@@ -310,28 +247,9 @@ def _launch(name: str, calls: List, *args):
         fn(calls[i:i + cap], *args)
 
 
-MULTI = True  # mixed-variant launches (module attribute: the per-variant path stays for A/B tests)
-# Deferred folds: the consumers right after a node's first reduction (the separable second stage's
-# input BN in the forward, the second-stage / dilated pointwise backward after combine_bwd_reduce)
-# sum the 32 replicas themselves in their prologue (workgroup-cooperative, one round trip:
-# darts_ops.hip coop_pair_sums), so those fold launches merge into the node's next fold
-# (False: fold before every consumer, as before; profiles/darts_defer_fold_ab_r03.log)
-DEFER_FOLD = True
-
-
 def _unfolded(bn):
     """The BN tuple of :func:`_bn` reading all REP replicas (its stats are not folded yet)."""
     return bn[:6] + (REP, bn[7])
-
-
-# a node's stage-1 separable + dilated depthwise backward in one mixed-variant launch, each part in
-# its own buffer, summed into gx by the pool-backward launch (profiles/darts_dwb_multi_ab_r03.log)
-DWB_MULTI = True
-# fused per-edge input gradient (edge_bwd_kernel) instead of per-family dw_bwd / pool_bwd launches.
-# Off by default: measured SLOWER on MI355X (B5 step 9.22 vs 8.05 ms; its 4 conv slots run
-# serially inside each workgroup, and fewer / larger bands only narrow the gap: 8.74 ms at 64 KB
-# bands), profiles/darts_selffold_edge_ab_r03.log. Kept for its numerics test (module attribute).
-EDGE_BWD = False
 
 
 # Needed-gradient pruning of the hand-scheduled backward (module attributes: tests and A/B runs flip
@@ -348,42 +266,15 @@ NEEDED_GRADS = True
 DROP_D = True
 
 
-# A node's pools launched beside its stage-1 dw-pw entries (one launch instead of two per node).
-# Off (module attribute, tests): measured a wash on the B5 step (6.98 vs 6.96 ms,
-# profiles/darts_vec_ab_r04.log) - the pool workgroups (highest blockIdx.y) dispatch after the dw-pw
-# bands anyway, so only the ~1.6 us launch boundary goes.
-JOINT_POOL = False
-
-
 def _dwpw_multi(entries):
     """dw-pw entries (x, dw, pw, inbn, d, z, stats, K, dil, S, pad) of one stage, mixed kernel sizes,
-    dilations and strides: one launch per 20 entries (per (K, dil, S) group with MULTI off)."""
-    if not entries:
-        return
-    if MULTI:
-        for i in range(0, len(entries), 20):
-            _K.dwpw_fwd_multi(entries[i:i + 20])
-        return
-    groups = defaultdict(list)
-    for e in entries:
-        groups[e[7:]].append(e[:7])
-    for (K, dil, S, pad), calls in groups.items():
-        _launch("dwpw_fwd", calls, K, dil, S, pad, True)
+    dilations and strides: one launch per 20 entries."""
+    _launch("dwpw_fwd_multi", entries)
 
 
 def _pool_multi(entries):
-    """pool_fwd entries (x, zavg, zmax, stats_avg, stats_max, amax, S) of both strides."""
-    if not entries:
-        return
-    if MULTI:
-        for i in range(0, len(entries), _CAP["pool_fwd"]):
-            _K.pool_fwd_multi(entries[i:i + _CAP["pool_fwd"]])
-        return
-    groups = defaultdict(list)
-    for e in entries:
-        groups[e[6]].append(e[:6])
-    for S, calls in groups.items():
-        _launch("pool_fwd", calls, S)
+    """pool_fwd_multi entries (x, zavg, zmax, stats_avg, stats_max, amax, S) of both strides."""
+    _launch("pool_fwd_multi", entries)
 
 
 class EdgeSpec:
@@ -405,7 +296,7 @@ class EdgeSpec:
 def _bn(stats: Optional[torch.Tensor], rm, rv, count: int, training: bool, eps: float, C: int):
     """BN reference tuple for the kernels; ``stats`` ([REP][2C]) is folded before use."""
     if training:  # under SyncBN the statistics are sums over every rank's batch
-        return (stats, rm, rv, 1.0 / (count * _world()), False, eps, _R, 2 * C)
+        return (stats, rm, rv, 1.0 / (count * _world()), False, eps, 1, 2 * C)
     return (None, rm, rv, 1.0 / count, True, eps, 1, 2 * C)
 
 
@@ -451,7 +342,6 @@ class _Edge:
         self.saved = {}
         self.id_idx, self.xid = -1, None
         self.upd = []
-        self.id_done = False
 
 
 def _node_forward(xs, ws, specs, bns, params_list, training, momentum, eps, out=None, extra_fold=(), grad=True):
@@ -461,7 +351,6 @@ def _node_forward(xs, ws, specs, bns, params_list, training, momentum, eps, out=
     state :func:`_node_backward` needs."""
     E = len(specs)
     xs = [t.contiguous() for t in xs]
-    _selffold(xs[0].device)  # before any producer launch: registers the counter ring on first use
     N, C = xs[0].shape[:2]
     S0 = specs[0].stride
     Ho = (xs[0].shape[2] - 1) // S0 + 1
@@ -552,18 +441,13 @@ def _node_forward(xs, ws, specs, bns, params_list, training, momentum, eps, out=
     # MI355X: B5 step 15.4 ms vs 13.05 ms sequential)
     dw1 = [(*c, K, dil, S, pad) for (K, dil, S, pad), calls in dw_groups.items() for c in calls]
     pools = [(*c, S) for S, calls in pool_groups.items() for c in calls]
-    if JOINT_POOL and MULTI and dw1 and pools and len(dw1) <= 20 and len(pools) <= _CAP["pool_fwd"]:
-        # the pools beside the stage-1 dw-pw bands in one launch (both read only the node inputs;
-        # the binding falls back to the two launches where the plane path does not apply)
-        _K.dwpw_pool_fwd_multi(dw1, pools)
-    else:
-        _dwpw_multi(dw1)
-        _pool_multi(pools)
+    _dwpw_multi(dw1)
+    _pool_multi(pools)
     if fr_calls:
         _launch("pw_fwd", fr_calls, 2)
-    defer = training and _defer(dev)
+    defer = training and _defer()
     if training and stage1 and not defer:
-        _fold64([(stats[i * slot:(i + 1) * slot], 2 * C, 2 * C) for i in sorted(set(stage1))], dev)
+        _fold([(stats[i * slot:(i + 1) * slot], 2 * C, 2 * C) for i in sorted(set(stage1))])
     # ---- separable stage 2 (stride 1, input BN-apply prologue)
     s2_groups = defaultdict(list)
     for e in edges:
@@ -580,8 +464,8 @@ def _node_forward(xs, ws, specs, bns, params_list, training, momentum, eps, out=
                 e.saved[prim] = (d1, z1, d2, z2)
     _dwpw_multi([(*c, K, 1, 1, K // 2) for K, calls in s2_groups.items() for c in calls])
     if training and (stage2 or (defer and stage1) or extra_fold):  # (deferred: the stage-1 statistics too)
-        _fold64([(stats[i * slot:(i + 1) * slot], 2 * C, 2 * C)
-                 for i in sorted(set(stage2 + (stage1 if defer else [])))] + list(extra_fold), dev)
+        _fold([(stats[i * slot:(i + 1) * slot], 2 * C, 2 * C)
+               for i in sorted(set(stage2 + (stage1 if defer else [])))] + list(extra_fold))
     # ---- weighted sums into the node output
     if out is None:
         out = torch.empty(N, C, Ho, Wo, device=dev)
@@ -642,17 +526,17 @@ def _node_backward(edges, training, C, dout, gx_of, take_first, sinks, pkey, cel
     _launch("combine_bwd_reduce", calls)
     # deferred: the pointwise backward right below sums the replicas itself and this fold joins
     # the separable second stages' fold (or runs after that pointwise launch)
-    defer = training and _defer(dev)
+    defer = training and _defer()
     # inside a cell every reader of this node's reductions sums the replicas itself, so the node
     # folds nothing: the d(alpha) segments go to the cell, which folds them once (if it needs them)
-    nofold = defer and cell_gw is not None and not EDGE_BWD
+    nofold = defer and cell_gw is not None
     if nofold:
         cell_gw.extend(gsegs)
-    if not _selffold(dev) and not defer:
-        _fold(segs if FOLD else gsegs)  # the d(alpha) segments are always folded
+    if not defer:
+        _fold(segs)
 
-    r_early = REP if defer else _R  # replicas the pointwise backward below reads
-    r_late = REP if nofold else _R  # ... and the pool / stride-2 skip backward further down
+    r_early = REP if defer else 1  # replicas the pointwise backward below reads
+    r_late = REP if nofold else 1  # ... and the pool / stride-2 skip backward further down
 
     def src(e, k, z, rep=r_late):  # GradSrc of a weighted, BN'd op output
         j = e.widx.index(k)
@@ -690,19 +574,12 @@ def _node_backward(edges, training, C, dout, gx_of, take_first, sinks, pkey, cel
             g, gst = sink(e, prim + ".1.dw")
             dw2[K].append((z1, e.refs[e.spec.slots[prim][0]], e.P[prim + ".1.dw"], dd2, g1, g, r1, gst, False))
             e.saved[prim + "/g1"] = (g1, r1)
-        _launch("pw_bwd", pw2 + (pwd if MULTI else []), 1, 0, True)
-        if not MULTI and pwd:
-            _launch("pw_bwd", pwd, 1, 0, True)
-        if MULTI:  # both kernel sizes in one launch (distinct g1 / red1 per entry)
-            allc = [(*c, K) for K, calls in dw2.items() for c in calls]
-            for i in range(0, len(allc), _CAP["dw_bwd"]):
-                _K.dw_bwd_multi(allc[i:i + _CAP["dw_bwd"]])
-        else:
-            for K, calls in dw2.items():
-                _launch("dw_bwd", calls, K, 1, 1, K // 2)
+        _launch("pw_bwd", pw2 + pwd, 1, 0, True)
+        # both kernel sizes in one launch (distinct g1 / red1 per entry)
+        _launch("dw_bwd_multi", [(*c, K) for K, calls in dw2.items() for c in calls])
         if training and not nofold:
-            _fold64([(red1[n * REP * 2 * C:(n + 1) * REP * 2 * C], 2 * C, 2 * C) for n in range(len(seps))]
-                    + (segs if defer else []), dev)
+            _fold([(red1[n * REP * 2 * C:(n + 1) * REP * 2 * C], 2 * C, 2 * C) for n in range(len(seps))]
+                  + (segs if defer else []))
         pw1 = []
         for e, k, prim in seps:
             d1, z1, d2, z2 = e.saved[prim]
@@ -715,8 +592,8 @@ def _node_backward(edges, training, C, dout, gx_of, take_first, sinks, pkey, cel
             pw1.append((gs1, e.P[prim + ".0.pw"], d1, e.x, dd1, None, g, 0, 0, gst))
         _launch("pw_bwd", pw1, 1, 0, True)
 
-    # ---- every edge's input gradient: stage-1 separable and dilated depthwise backward, pools and
-    # the identity skip in ONE fused launch (edge_bwd_kernel), else the per-family launches below
+    # ---- every edge's input gradient: stage-1 separable and dilated depthwise backward, then pools
+    # and the identity skip
     first = {e.i: take_first(e.i) for e in edges}
 
     def tf(i):  # the first writer of gx_of(i) overwrites it
@@ -734,95 +611,28 @@ def _node_backward(edges, training, C, dout, gx_of, take_first, sinks, pkey, cel
                 gm = src(e, k, zm)
         return ga, gm, am
 
-    if EDGE_BWD:
-        entries = []
-        for e in edges:
-            convs = [None] * 4
-            for k, prim in enumerate(e.spec.prims):
-                if prim.startswith("separable_convolution"):
-                    g, gst = sink(e, prim + ".0.dw")
-                    convs[0 if prim[-1] == "3" else 1] = (e.P[prim + ".0.dw"], e.saved[prim + "/dd1"], g, gst)
-                elif prim.startswith("dilated_convolution"):
-                    g, gst = sink(e, prim + ".dw")
-                    convs[2 if prim[-1] == "3" else 3] = (e.P[prim + ".dw"], dd_of[(e.i, prim)], g, gst)
-            ga, gm, am = pool_srcs(e) if "pool" in e.saved else (None, None, None)
-            entries.append((e.x, gxs[e.i], first[e.i], convs, ga, gm, am, dout if e.id_idx >= 0 else None, e.w,
-                            e.id_idx, e.S))
-        ok = True
-        for i in range(0, len(entries), 4):
-            ok = ok and bool(_K.edge_bwd(entries[i:i + 4]))
-        if ok:
-            for e in edges:
-                first[e.i] = False
-        elif len(entries) > 4:  # a partial launch cannot be undone: fail loudly
-            raise RuntimeError("edge_bwd accepted part of a node's edges")
-    if (not EDGE_BWD or not ok) and MULTI and DWB_MULTI:
-        # every stage-1 separable and dilated depthwise backward of the node in ONE mixed-variant
-        # launch, each into its own buffer (no read-modify-write of gx, so no ordering between
-        # them); the pool-backward launch then forms gx = pools + identity + those parts, once
-        convs, parts = [], defaultdict(list)
-        for e, k, prim in seps + dils:
-            sep = prim.startswith("separable_convolution")
-            K = int(prim[-1])
-            t = torch.empty_like(e.x)
-            parts[e.i].append(t)
-            name = prim + (".0.dw" if sep else ".dw")
-            g, gst = sink(e, name)
-            dd = e.saved[prim + "/dd1"] if sep else dd_of[(e.i, prim)]
-            convs.append((e.x, None, e.P[name], dd, t, g, None, gst, True, K, 1 if sep else 2, e.S))
-        for i in range(0, len(convs), _CAP["dw_bwd"]):
-            _K.dw_bwd_multi(convs[i:i + _CAP["dw_bwd"]])
-        sums = []
-        for e in edges:
-            ga, gm, am = pool_srcs(e) if "pool" in e.saved else (None, None, None)
-            ex = parts.get(e.i, [])
-            if ga is None and gm is None and e.id_idx < 0 and not ex:
-                continue  # only a stride-2 skip (below) or 'none' writes this edge's gradient
-            sums.append((ga, gm, e.x, dout if e.id_idx >= 0 else None, e.w, e.id_idx, gxs[e.i], am, tf(e.i), e.S, ex))
-            e.id_done = True
-        for i in range(0, len(sums), _CAP["pool_bwd"]):
-            _K.pool_bwd_multi(sums[i:i + _CAP["pool_bwd"]])
-    elif not EDGE_BWD or not ok:
-        if seps:
-            dw1 = defaultdict(list)
-            for e, k, prim in seps:
-                K = int(prim[-1])
-                g, gst = sink(e, prim + ".0.dw")
-                dw1[(K, e.S)].append((e.x, None, e.P[prim + ".0.dw"], e.saved[prim + "/dd1"], gxs[e.i], g, None, gst,
-                                      tf(e.i)))
-            for (K, S), calls in dw1.items():
-                _launch("dw_bwd", calls, K, 1, S, K // 2)
-        # ---- dilated convs (depthwise backward; the pointwise part ran above)
-        if dils:
-            dwd = defaultdict(list)
-            for e, k, prim in dils:
-                K = int(prim[-1])
-                g, gst = sink(e, prim + ".dw")
-                dwd[(K, e.S)].append((e.x, None, e.P[prim + ".dw"], dd_of[(e.i, prim)], gxs[e.i], g, None, gst,
-                                      tf(e.i)))
-            for (K, S), calls in dwd.items():
-                _launch("dw_bwd", calls, K, 2, S, (K // 2) * 2)
-        # ---- pools (+ the identity skip of stride-1 edges)
-        pools = defaultdict(list)
-        for e in edges:
-            if "pool" not in e.saved:
-                continue
-            ga, gm, am = pool_srcs(e)
-            pools[e.S].append((ga, gm, e.x, dout if e.id_idx >= 0 else None, e.w, e.id_idx, gxs[e.i], am, tf(e.i)))
-            e.id_done = True
-        if MULTI:  # both strides in one launch (entries are distinct edges: distinct gx buffers)
-            allp = [(*c, S) for S, calls in pools.items() for c in calls]
-            for i in range(0, len(allp), _CAP["pool_bwd"]):
-                _K.pool_bwd_multi(allp[i:i + _CAP["pool_bwd"]])
-        else:
-            for S, calls in pools.items():
-                _launch("pool_bwd", calls, S)
-        for e in edges:
-            if e.id_idx >= 0 and not e.id_done:
-                if tf(e.i):
-                    torch.mul(dout, e.w[e.id_idx], out=gxs[e.i])
-                else:
-                    gxs[e.i].add_(dout * e.w[e.id_idx])
+    # every stage-1 separable and dilated depthwise backward of the node in ONE mixed-variant
+    # launch, each into its own buffer (no read-modify-write of gx, so no ordering between
+    # them); the pool-backward launch then forms gx = pools + identity + those parts, once
+    convs, parts = [], defaultdict(list)
+    for e, k, prim in seps + dils:
+        sep = prim.startswith("separable_convolution")
+        K = int(prim[-1])
+        t = torch.empty_like(e.x)
+        parts[e.i].append(t)
+        name = prim + (".0.dw" if sep else ".dw")
+        g, gst = sink(e, name)
+        dd = e.saved[prim + "/dd1"] if sep else dd_of[(e.i, prim)]
+        convs.append((e.x, None, e.P[name], dd, t, g, None, gst, True, K, 1 if sep else 2, e.S))
+    _launch("dw_bwd_multi", convs)
+    sums = []
+    for e in edges:
+        ga, gm, am = pool_srcs(e) if "pool" in e.saved else (None, None, None)
+        ex = parts.get(e.i, [])
+        if ga is None and gm is None and e.id_idx < 0 and not ex:
+            continue  # only a stride-2 skip (below) or 'none' writes this edge's gradient
+        sums.append((ga, gm, e.x, dout if e.id_idx >= 0 else None, e.w, e.id_idx, gxs[e.i], am, tf(e.i), e.S, ex))
+    _launch("pool_bwd_multi", sums)
     # ---- stride-2 skip (FactorizedReduce): scattered adds, so its gx must exist already
     frc = []
     for e in edges:
@@ -917,7 +727,6 @@ def _stdconv_forward(x, rm, rv, training, momentum, eps, w1, w2, defer=None):
     the replicas itself and the fold segment is appended to ``defer`` for the cell's first node's
     fold; the backward then reads them folded."""
     x = x.contiguous()
-    _selffold(x.device)
     N, Cin, H, W = _dims(x)
     fr = w2 is not None
     Cout = w1.shape[0] * (2 if fr else 1)
@@ -930,9 +739,9 @@ def _stdconv_forward(x, rm, rv, training, momentum, eps, w1, w2, defer=None):
     else:
         _K.pw_fwd([(x, w1, z, stats, 0, 0)], 1)
     bn = _bn(stats, rm, rv, cnt, training, eps, Cout)
-    late = defer is not None and training and _defer(x.device)
+    late = defer is not None and training and _defer()
     if training and not late:
-        _fold64([(stats, 2 * Cout, 2 * Cout)], x.device)
+        _fold([(stats, 2 * Cout, 2 * Cout)])
     if late:
         defer.append((stats, 2 * Cout, 2 * Cout))
     out = torch.empty(z.shape, device=x.device)
@@ -951,12 +760,12 @@ def _stdconv_backward(state, dout, need_x, sinks, keys, gx=None, first=True):
     red = zeros64(REP * nred, x.device)
     # deferred: the pointwise backward (its only consumer) sums the replicas in its prologue, and
     # nothing reads them later, so this fold goes away (the arena is re-zeroed every step)
-    late = training and _defer(x.device)
+    late = training and _defer()
     if training:
         _K.combine_bwd_reduce([(dout, [z], [bn], None, red, [0], -1, None)])
         if not late:
-            _fold64([(red, nred, nred)], x.device)
-    gs = (dout, z, red[:Cout], red[Cout:2 * Cout], bn, None, 0, REP if late else _R, nred)
+            _fold([(red, nred, nred)])
+    gs = (dout, z, red[:Cout], red[Cout:2 * Cout], bn, None, 0, REP if late else 1, nred)
     g1, s1 = sinks.get(w1, keys[0])
     given = gx is not None
     if fr:  # the two stride-2 grids leave 2 of 4 input pixels untouched: start from zeros
@@ -1267,8 +1076,7 @@ def _stem_bwd(state, dout, sinks, keys, need):
     nred = 2 * C + 1
     red = zeros64(REP * nred, x.device)
     _K.combine_bwd_reduce([(dout, [zs], [bn], None, red, [0], -1, None)])
-    if not _selffold(x.device):
-        _fold([(red, nred, nred)])
+    _fold([(red, nred, nred)])
     gg, _ = sinks.get(gamma, keys[1]) if need[2] else (None, 0)
     gb, _ = sinks.get(beta, keys[2]) if need[3] else (None, 0)
     gw = gx = None
@@ -1585,10 +1393,9 @@ class _Network(torch.autograd.Function):
 # Under SyncBN the twin folds become one fold + cross-rank sum: one rendezvous instead of two.
 # Reference: the architect's Hessian-vector product, examples/v1beta1/trial-images/darts-cnn-cifar10/
 # architect.py:98-135 (two forward/backward passes at w +- eps dw').
-_MERGE_CAP = {"dwpw_fwd": 16, "pw_fwd": 32, "pool_fwd": 16, "combine_bwd_reduce": 8, "pw_bwd": 32, "dw_bwd": 40,
-              "pool_bwd": 16, "dw_bwd_multi": 40, "dwpw_fwd_multi": 40, "pool_fwd_multi": 16,
-              "pool_bwd_multi": 16, "fold_f64": 128, "alpha_grad": 128, "__sync_fold__": 64}
-_QUERIES = {"selffold_ready", "max_blocks", "stamps_compiled", "REP", "ZBF16", "OPTIM_MAX_PARTS", "dwpw_split_path"}
+_MERGE_CAP = {"pw_fwd": 32, "combine_bwd_reduce": 8, "pw_bwd": 32, "dw_bwd_multi": 40, "dwpw_fwd_multi": 40,
+              "pool_fwd_multi": 16, "pool_bwd_multi": 16, "fold_f64": 128, "alpha_grad": 128, "__sync_fold__": 64}
+_QUERIES = {"max_blocks", "stamps_compiled", "REP", "ZBF16", "OPTIM_MAX_PARTS", "dwpw_split_path"}
 
 
 class _Recorder:
@@ -1635,11 +1442,6 @@ class stacked_passes:
     @contextlib.contextmanager
     def pass_(self):
         global _K, _SYNC
-        if EDGE_BWD or JOINT_POOL or SELFFOLD:
-            # opt-in paths that branch on launch return values or attach per-launch fold tails:
-            # the passes run live, one after the other
-            yield
-            return
         tape: list = []
         self.tapes.append(tape)
         real_k, real_sync = _K, _SYNC

@@ -104,12 +104,10 @@ def test_darts_dp_syncbn_matches_single_process():
     assert per_rank["dA"] > 10 * max(res["dA"], 1e-12), (per_rank, res)
 
 
-def test_syncbn_rejects_fold_modes_without_cross_rank_sum(monkeypatch):
-    """under SyncBN ``_bn`` divides by count * world, which is only right when the fold
-    launch summed the BN reductions over the ranks. FOLD=0 and self-folding producers skip that
-    fold, so SyncBN and sync_scope refuse them instead of normalising with local sums / world."""
-    import pytest
-
+def test_syncbn_constructs_and_sync_scope_restores():
+    """``SyncBN`` constructs on a communicator without the one-shot xGMI path, and ``sync_scope``
+    sets the module's SyncBN state for its block and restores the previous one on exit, nested
+    scopes included (``None`` inside a SyncBN scope: per-rank BN for that block)."""
     from katib_amd.ops import hip_darts as h
 
     class FakeComm:
@@ -121,21 +119,16 @@ def test_syncbn_rejects_fold_modes_without_cross_rank_sum(monkeypatch):
         def probe_rccl_capture(self):
             return False
 
-    sync = h.SyncBN(FakeComm())  # default modes: accepted
-    monkeypatch.setattr(h, "FOLD", False)
-    with pytest.raises(RuntimeError, match="hip_darts.FOLD"):
-        h.SyncBN(FakeComm())
-    with pytest.raises(RuntimeError, match="hip_darts.FOLD"):
-        with h.sync_scope(sync):
-            pass
-    monkeypatch.setattr(h, "FOLD", True)
-    monkeypatch.setattr(h, "SELFFOLD", True)
-    with pytest.raises(RuntimeError, match="SELFFOLD"):
-        with h.sync_scope(sync):
-            pass
-    monkeypatch.setattr(h, "SELFFOLD", False)
+    sync = h.SyncBN(FakeComm())
+    assert sync.world == 2
+    assert h._SYNC is None and h._world() == 1
     with h.sync_scope(sync):
-        with pytest.raises(RuntimeError, match="SyncBN"):
-            h.set_selffold(True)
-    with h.sync_scope(None):  # per-rank BN: any fold mode
-        pass
+        assert h._SYNC is sync and h._world() == 2
+        with h.sync_scope(None):
+            assert h._SYNC is None
+        assert h._SYNC is sync
+        inner = h.SyncBN(FakeComm())
+        with h.sync_scope(inner):
+            assert h._SYNC is inner
+        assert h._SYNC is sync
+    assert h._SYNC is None
