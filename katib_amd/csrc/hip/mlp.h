@@ -17,9 +17,19 @@ hipError_t lin_fwd(const bf16* x, const int64_t* idx, const bf16* w, const float
 hipError_t lin_wgrad_sgd(const bf16* dy, const bf16* x, const int64_t* idx, int M, int N, int K, float* w, float* wm,
                          bf16* w16, bf16* w16t, float* bias, float* bm, const float* lr, float momentum,
                          hipStream_t st);
+// The same reduction with torch.optim.Adam (default flags) in the epilogue: m / v [N][K] fp32, bm / bv [N];
+// t = step_t[0] is the 1-based number of the running step (device int32, advanced by xent_small).
+hipError_t lin_wgrad_adam(const bf16* dy, const bf16* x, const int64_t* idx, int M, int N, int K, float* w, float* m,
+                          float* v, bf16* w16, bf16* w16t, float* bias, float* bm, float* bv, const float* lr,
+                          const int* step_t, float beta1, float beta2, float eps, hipStream_t st);
+// ... and with FTRL-proximal (workloads/mnist_mlp.py Ftrl): z / n [N][K] fp32, bz / bn [N].
+hipError_t lin_wgrad_ftrl(const bf16* dy, const bf16* x, const int64_t* idx, int M, int N, int K, float* w, float* z,
+                          float* n, bf16* w16, bf16* w16t, float* bias, float* bz, float* bn, const float* lr,
+                          float l1, float beta, float wd, hipStream_t st);
 // softmax cross-entropy over the first C of ld columns; dl = (softmax - onehot) / M; stats += (mean loss, correct).
+// step_t (may be null): device int32 step counter, incremented once per launch.
 hipError_t xent_small(const bf16* logits, const int64_t* y, const int64_t* idx, bf16* dl, int M, int C, int ld,
-                      float* stats, hipStream_t st);
+                      float* stats, int* step_t, hipStream_t st);
 
 }  // namespace mlp
 }  // namespace katib_hip

@@ -1,7 +1,7 @@
 // Fused MLP training kernels for gfx950 (BASELINE config 2: TPE over lr / batch size / width
-// of an MNIST MLP). One train step of 784 -> h -> h/2 -> 10 is nine launches,
-// all graph-captured, with no separate bias, activation, gather, cast, loss or optimizer
-// kernels:
+// of an MNIST MLP; and the B1 search space: depth and optimizer). One train step
+// of an MLP with L hidden layers is 3L + 3 launches (nine for 784 -> h -> h/2 -> 10), all
+// graph-captured, with no separate bias, activation, gather, cast, loss or optimizer kernels:
 //
 //  lin_fwd    Y = act(X W^T + b): bf16 MFMA (v_mfma_f32_16x16x32_bf16) over K-contiguous
 //             operands staged through padded LDS rows; optional row gather of X (the
@@ -10,13 +10,22 @@
 //             transposed bf16 weight shadow as the K-contiguous operand).
 //  lin_wgrad  dW = dY^T X reduced over the whole minibatch inside one workgroup (the
 //             minibatch is the reduction, <= a few hundred rows), both operands read with
-//             ds_read_b64_tr_b16, and SGD-with-momentum applied in the epilogue: fp32
-//             master, momentum buffer, bf16 weight and transposed-weight shadows; the
-//             workgroups of the first K tile also reduce and update the bias.
-//  xent_small cross-entropy + its gradient for a handful of classes, one lane per row.
+//             ds_read_b64_tr_b16, and the optimizer applied in the epilogue to the fp32
+//             master and its state, with the bf16 weight and transposed-weight shadows
+//             refreshed; the workgroups of the first K tile also reduce and update the bias.
+//             One templated kernel (wgrad_k), three epilogues over its main loop: SGD with
+//             momentum (wgrad_k<float>), Adam and FTRL-proximal (wgrad_k<Opt2<AdamUpd>>,
+//             wgrad_k<Opt2<FtrlUpd>>). The latter two issue all of a thread's 48 state loads
+//             before the first arithmetic.
+//  xent_small cross-entropy + its gradient for a handful of classes, one lane per row. It
+//             runs once per step between the previous step's last weight-gradient launch
+//             and this step's first, so it is also where the device step counter (Adam's
+//             t) advances: thread 0 of block 0 adds 1 when a counter is given.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "mlp.h"
 
@@ -131,15 +140,72 @@ __global__ __launch_bounds__(256) void gemm_nt_k(const u16* __restrict__ A, cons
     }
 }
 
-// ------------------------------------------------------------------ dW = dY^T X, fused SGD
+// Element updates of the two-state optimizers: operator() takes the gradient, the element's two
+// state values (updated in place) and its weight, and returns the new weight. Both leave an
+// element with g = 0 and zero state exactly as it was (the padded output rows, dead ReLU units).
+//
+// torch.optim.Adam, default flags: s0 = exp_avg, s1 = exp_avg_sq. step = lr / (1 - beta1^t) and
+// sbc2 = sqrt(1 - beta2^t) are the same for every element; init() computes them once per thread.
+struct AdamUpd {
+  float b1, b2, eps;
+  const int* step_t;
+  float step, sbc2;
+  // beta^t by binary exponentiation: exact at t = 1, where 1 - beta2^t = 1e-3 magnifies an error of
+  // beta2^t a thousandfold, and within t * 2^-24 relative anywhere
+  static __device__ __forceinline__ float ipow(float b, int t) {
+    float r = 1.f;
+    for (; t > 0; t >>= 1, b *= b)
+      if (t & 1) r *= b;
+    return r;
+  }
+  __device__ __forceinline__ void init(float lr) {
+    const int t = max(step_t[0], 1);  // 1-based; a counter nobody advanced must not divide by 0
+    step = lr / (1.f - ipow(b1, t));
+    sbc2 = sqrtf(1.f - ipow(b2, t));
+  }
+  __device__ __forceinline__ float operator()(float g, float& m, float& v, float w) const {
+    m = b1 * m + (1.f - b1) * g;
+    v = b2 * v + (1.f - b2) * (g * g);
+    return w - step * (m / (sqrtf(v) / sbc2 + eps));  // zero state, g = 0: 0 / eps = 0
+  }
+};
+// The trial's Ftrl class (FTRL-proximal as MXNet's), operation for operation: s0 = z, s1 = n.
+struct FtrlUpd {
+  float l1, beta, wd;
+  float lr;
+  __device__ __forceinline__ void init(float lr_) { lr = lr_; }
+  __device__ __forceinline__ float operator()(float g, float& z, float& n, float w) const {
+    const float sq_old = sqrtf(n);
+    n += g * g;  // n only grows from >= 0: both square roots are of non-negative numbers
+    const float sq = sqrtf(n);
+    z += g - (sq - sq_old) / lr * w;
+    const float sgn = z > 0.f ? 1.f : (z < 0.f ? -1.f : 0.f);
+    return fabsf(z) > l1 ? (sgn * l1 - z) / ((beta + sq) / lr + wd) : 0.f;  // zero state, g = 0: z = 0, w = 0
+  }
+};
+
+// A two-state optimizer as the kernel's last argument: the element update and the second state arrays.
+template <class U>
+struct Opt2 {
+  typedef U Upd;
+  U upd;
+  float* s1;
+  float* bs1;
+};
+
+// ------------------------------------------------------------------ dW = dY^T X, fused optimizers
 // dY [M][N] bf16, X [M][K] bf16 (rows gathered through idx when given), W [N][K] fp32 master.
-// One workgroup per 64 x 64 tile of W, reducing over all M rows.
-__global__ __launch_bounds__(256) void wgrad_sgd_k(const u16* __restrict__ dY, const u16* __restrict__ X,
-                                                   const int64_t* __restrict__ idx, int M, int N, int K,
-                                                   float* __restrict__ W, float* __restrict__ Wm,
-                                                   u16* __restrict__ W16, u16* __restrict__ W16t,
-                                                   float* __restrict__ bias, float* __restrict__ bm,
-                                                   const float* __restrict__ lr_p, float mom) {
+// One workgroup per 64 x 64 tile of W, reducing over all M rows. One kernel, three epilogues,
+// chosen by the type of the last argument: float = SGD with momentum (S0 = the momentum buffer;
+// this instantiation has the argument layout and the body the SGD-only kernel had), Opt2<U> = a
+// two-state optimizer U (S0 and the Opt2's s1: Adam's m, v or FTRL's z, n).
+template <class E>
+__global__ __launch_bounds__(256) void wgrad_k(const u16* __restrict__ dY, const u16* __restrict__ X,
+                                               const int64_t* __restrict__ idx, int M, int N, int K,
+                                               float* __restrict__ W, float* __restrict__ S0,
+                                               u16* __restrict__ W16, u16* __restrict__ W16t,
+                                               float* __restrict__ bias, float* __restrict__ bs0,
+                                               const float* __restrict__ lr_p, E e) {
   constexpr int BP = 64;
   constexpr int LDA = BN + PAD, LDB = BK + PAD;
   __shared__ __align__(16) u16 smem[2 * BP * (LDA + LDB)];
@@ -222,46 +288,110 @@ __global__ __launch_bounds__(256) void wgrad_sgd_k(const u16* __restrict__ dY, c
     __syncthreads();
     buf ^= 1;
   }
-  const float lr = lr_p[0];
-  // SGD with momentum (torch semantics, dampening 0): buf = mom * buf + g; p -= lr * buf
+  if constexpr (std::is_same<E, float>::value) {
+    const float mom = e;
+    const float lr = lr_p[0];
+    // SGD with momentum (torch semantics, dampening 0): buf = mom * buf + g; p -= lr * buf
 #pragma unroll
-  for (int a = 0; a < 2; ++a)
+    for (int a = 0; a < 2; ++a)
 #pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const int k = k0 + wc * 32 + b * 16 + (lane & 15);
-      if (k >= K) continue;
+      for (int b = 0; b < 2; ++b) {
+        const int k = k0 + wc * 32 + b * 16 + (lane & 15);
+        if (k >= K) continue;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int n = n0 + wr * 32 + a * 16 + 4 * (lane >> 4) + j;
-        if (n >= N) continue;
-        const int64_t o = (int64_t)n * K + k;
-        const float mb = mom * Wm[o] + acc[a][b][j];
-        const float p = W[o] - lr * mb;
-        Wm[o] = mb;
-        W[o] = p;
-        const u16 pb = f2bf(p);
-        W16[o] = pb;
-        W16t[(int64_t)k * N + n] = pb;
+        for (int j = 0; j < 4; ++j) {
+          const int n = n0 + wr * 32 + a * 16 + 4 * (lane >> 4) + j;
+          if (n >= N) continue;
+          const int64_t o = (int64_t)n * K + k;
+          const float mb = mom * S0[o] + acc[a][b][j];
+          const float p = W[o] - lr * mb;
+          S0[o] = mb;
+          W[o] = p;
+          const u16 pb = f2bf(p);
+          W16[o] = pb;
+          W16t[(int64_t)k * N + n] = pb;
+        }
+      }
+    if (do_bias) {
+      bsum[tid >> 6][tid & 63] = bacc;
+      __syncthreads();
+      if (tid < 64 && n0 + tid < N) {
+        const float g = (bsum[0][tid] + bsum[1][tid]) + (bsum[2][tid] + bsum[3][tid]);
+        const float mb = mom * bs0[n0 + tid] + g;
+        bs0[n0 + tid] = mb;
+        bias[n0 + tid] -= lr * mb;
       }
     }
-  if (do_bias) {
-    bsum[tid >> 6][tid & 63] = bacc;
-    __syncthreads();
-    if (tid < 64 && n0 + tid < N) {
-      const float g = (bsum[0][tid] + bsum[1][tid]) + (bsum[2][tid] + bsum[3][tid]);
-      const float mb = mom * bm[n0 + tid] + g;
-      bm[n0 + tid] = mb;
-      bias[n0 + tid] -= lr * mb;
+  } else {
+    using U = typename E::Upd;
+    U upd = e.upd;
+    upd.init(lr_p[0]);
+    float* __restrict__ S1 = e.s1;
+    float* __restrict__ bs1 = e.bs1;
+    float w[2][2][4], s0[2][2][4], s1[2][2][4];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int k = k0 + wc * 32 + b * 16 + (lane & 15);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int n = n0 + wr * 32 + a * 16 + 4 * (lane >> 4) + j;
+          const bool in = k < K && n < N;
+          const int64_t o = in ? (int64_t)n * K + k : 0;
+          w[a][b][j] = in ? W[o] : 0.f;
+          s0[a][b][j] = in ? S0[o] : 0.f;
+          s1[a][b][j] = in ? S1[o] : 0.f;
+        }
+      }
+    float bw = 0.f, b0 = 0.f, b1 = 0.f;
+    const bool bias_lane = do_bias && tid < 64 && n0 + tid < N;
+    if (bias_lane) {
+      bw = bias[n0 + tid];
+      b0 = bs0[n0 + tid];
+      b1 = bs1[n0 + tid];
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const int k = k0 + wc * 32 + b * 16 + (lane & 15);
+        if (k >= K) continue;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int n = n0 + wr * 32 + a * 16 + 4 * (lane >> 4) + j;
+          if (n >= N) continue;
+          const int64_t o = (int64_t)n * K + k;
+          const float p = upd(acc[a][b][j], s0[a][b][j], s1[a][b][j], w[a][b][j]);
+          S0[o] = s0[a][b][j];
+          S1[o] = s1[a][b][j];
+          W[o] = p;
+          const u16 pb = f2bf(p);
+          W16[o] = pb;
+          W16t[(int64_t)k * N + n] = pb;
+        }
+      }
+    if (do_bias) {
+      bsum[tid >> 6][tid & 63] = bacc;
+      __syncthreads();
+      if (bias_lane) {
+        const float g = (bsum[0][tid] + bsum[1][tid]) + (bsum[2][tid] + bsum[3][tid]);
+        bias[n0 + tid] = upd(g, b0, b1, bw);
+        bs0[n0 + tid] = b0;
+        bs1[n0 + tid] = b1;
+      }
     }
   }
 }
 
 // ------------------------------------------------------------------ softmax cross-entropy, few classes
 // logits [M][ld] bf16 (first C columns real); dlogits = (softmax - onehot) / M (pad columns 0);
-// stats[0] += sum of losses / M, stats[1] += number of correct argmax predictions.
+// stats[0] += sum of losses / M, stats[1] += number of correct argmax predictions. step_t (may be
+// null): the device step counter, advanced by one per launch; nothing else reads or writes it here.
 __global__ __launch_bounds__(256) void xent_small_k(const u16* __restrict__ logits, const int64_t* __restrict__ y,
                                                     const int64_t* __restrict__ idx, u16* __restrict__ dl, int M,
-                                                    int C, int ld, float* __restrict__ stats) {
+                                                    int C, int ld, float* __restrict__ stats,
+                                                    int* __restrict__ step_t) {
   __shared__ float red[2][4];
   const int r = blockIdx.x * 256 + threadIdx.x;
   float loss = 0.f, correct = 0.f;
@@ -298,6 +428,7 @@ __global__ __launch_bounds__(256) void xent_small_k(const u16* __restrict__ logi
   if (threadIdx.x == 0) {
     atomicAdd(stats, (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]));
     atomicAdd(stats + 1, (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]));
+    if (step_t != nullptr && blockIdx.x == 0) step_t[0] += 1;
   }
 }
 
@@ -316,16 +447,40 @@ hipError_t lin_wgrad_sgd(const bf16* dy, const bf16* x, const int64_t* idx, int 
                          bf16* w16, bf16* w16t, float* bias, float* bm, const float* lr, float momentum,
                          hipStream_t st) {
   const int grid = ((N + BN - 1) / BN) * ((K + BK - 1) / BK);
-  hipLaunchKernelGGL(wgrad_sgd_k, dim3(grid), dim3(256), 0, st, reinterpret_cast<const u16*>(dy),
+  hipLaunchKernelGGL(wgrad_k<float>, dim3(grid), dim3(256), 0, st, reinterpret_cast<const u16*>(dy),
                      reinterpret_cast<const u16*>(x), idx, M, N, K, w, wm, reinterpret_cast<u16*>(w16),
                      reinterpret_cast<u16*>(w16t), bias, bm, lr, momentum);
   return hipGetLastError();
 }
 
+template <class U>
+static hipError_t launch_wgrad_opt(const bf16* dy, const bf16* x, const int64_t* idx, int M, int N, int K, float* w,
+                                   float* s0, float* s1, bf16* w16, bf16* w16t, float* bias, float* bs0, float* bs1,
+                                   const float* lr, U upd, hipStream_t st) {
+  const int grid = ((N + BN - 1) / BN) * ((K + BK - 1) / BK);
+  hipLaunchKernelGGL(wgrad_k<Opt2<U>>, dim3(grid), dim3(256), 0, st, reinterpret_cast<const u16*>(dy),
+                     reinterpret_cast<const u16*>(x), idx, M, N, K, w, s0, reinterpret_cast<u16*>(w16),
+                     reinterpret_cast<u16*>(w16t), bias, bs0, lr, Opt2<U>{upd, s1, bs1});
+  return hipGetLastError();
+}
+
+hipError_t lin_wgrad_adam(const bf16* dy, const bf16* x, const int64_t* idx, int M, int N, int K, float* w, float* m,
+                          float* v, bf16* w16, bf16* w16t, float* bias, float* bm, float* bv, const float* lr,
+                          const int* step_t, float beta1, float beta2, float eps, hipStream_t st) {
+  return launch_wgrad_opt(dy, x, idx, M, N, K, w, m, v, w16, w16t, bias, bm, bv, lr,
+                          AdamUpd{beta1, beta2, eps, step_t, 0.f, 0.f}, st);
+}
+
+hipError_t lin_wgrad_ftrl(const bf16* dy, const bf16* x, const int64_t* idx, int M, int N, int K, float* w, float* z,
+                          float* n, bf16* w16, bf16* w16t, float* bias, float* bz, float* bn, const float* lr,
+                          float l1, float beta, float wd, hipStream_t st) {
+  return launch_wgrad_opt(dy, x, idx, M, N, K, w, z, n, w16, w16t, bias, bz, bn, lr, FtrlUpd{l1, beta, wd, 0.f}, st);
+}
+
 hipError_t xent_small(const bf16* logits, const int64_t* y, const int64_t* idx, bf16* dl, int M, int C, int ld,
-                      float* stats, hipStream_t st) {
+                      float* stats, int* step_t, hipStream_t st) {
   hipLaunchKernelGGL(xent_small_k, dim3((M + 255) / 256), dim3(256), 0, st, reinterpret_cast<const u16*>(logits), y,
-                     idx, reinterpret_cast<u16*>(dl), M, C, ld, stats);
+                     idx, reinterpret_cast<u16*>(dl), M, C, ld, stats, step_t);
   return hipGetLastError();
 }
 

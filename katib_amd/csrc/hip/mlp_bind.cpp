@@ -73,8 +73,78 @@ void lin_wgrad_sgd(const Tensor& dy, const Tensor& x, const c10::optional<Tensor
      "lin_wgrad_sgd");
 }
 
+// the operands every fused weight-gradient kernel shares; returns (M, N, K)
+struct WgShape {
+  int64_t M, N, K;
+};
+WgShape chk_wgrad(const char* who, const Tensor& dy, const Tensor& x, const c10::optional<Tensor>& idx, const Tensor& w,
+                  const Tensor& w16, const Tensor& w16t, const Tensor& lr) {
+  TORCH_CHECK(dy.dim() == 2 && x.dim() == 2 && w.dim() == 2, who, ": 2-D operands");
+  const int64_t M = dy.size(0), N = dy.size(1), K = w.size(1);
+  TORCH_CHECK(w.size(0) == N && x.size(1) == K && N % 8 == 0 && K % 8 == 0, who, ": N, K % 8 == 0");
+  TORCH_CHECK(idx.has_value() || x.size(0) == M, who, ": x rows must match dy rows without a gather");
+  chk(dy, at::kBFloat16, M * N, "dy");
+  chk(x, at::kBFloat16, x.numel(), "x");
+  chk_idx(idx, M);
+  chk(w, at::kFloat, N * K, "w");
+  chk(w16, at::kBFloat16, N * K, "w16");
+  chk(w16t, at::kBFloat16, N * K, "w16t");
+  TORCH_CHECK(lr.is_cuda() && lr.scalar_type() == at::kFloat && lr.numel() == 1, "lr must be a GPU fp32 scalar");
+  return {M, N, K};
+}
+// bias and its two state vectors: together or not at all
+bool chk_bias2(const c10::optional<Tensor>& bias, const c10::optional<Tensor>& s0, const c10::optional<Tensor>& s1,
+               int64_t N, const char* n0, const char* n1) {
+  TORCH_CHECK(bias.has_value() == s0.has_value() && bias.has_value() == s1.has_value(),
+              "bias and its two state vectors go together");
+  if (!bias.has_value()) return false;
+  chk(*bias, at::kFloat, N, "bias");
+  chk(*s0, at::kFloat, N, n0);
+  chk(*s1, at::kFloat, N, n1);
+  return true;
+}
+const int64_t* idx_p(const c10::optional<Tensor>& idx) { return idx.has_value() ? idx->data_ptr<int64_t>() : nullptr; }
+void chk_step_t(const Tensor& step_t) {
+  TORCH_CHECK(step_t.is_cuda() && step_t.scalar_type() == at::kInt && step_t.numel() == 1,
+              "step_t must be a GPU int32 tensor of one element");
+}
+
+void lin_wgrad_adam(const Tensor& dy, const Tensor& x, const c10::optional<Tensor>& idx, const Tensor& w,
+                    const Tensor& m, const Tensor& v, const Tensor& w16, const Tensor& w16t,
+                    const c10::optional<Tensor>& bias, const c10::optional<Tensor>& bm,
+                    const c10::optional<Tensor>& bv, const Tensor& lr, const Tensor& step_t, double beta1,
+                    double beta2, double eps) {
+  const WgShape s = chk_wgrad("lin_wgrad_adam", dy, x, idx, w, w16, w16t, lr);
+  chk(m, at::kFloat, s.N * s.K, "m");
+  chk(v, at::kFloat, s.N * s.K, "v");
+  const bool hb = chk_bias2(bias, bm, bv, s.N, "bm", "bv");
+  chk_step_t(step_t);
+  ok(M_::lin_wgrad_adam(bp(dy), bp(x), idx_p(idx), (int)s.M, (int)s.N, (int)s.K, w.data_ptr<float>(),
+                        m.data_ptr<float>(), v.data_ptr<float>(), bp(w16), bp(w16t),
+                        hb ? bias->data_ptr<float>() : nullptr, hb ? bm->data_ptr<float>() : nullptr,
+                        hb ? bv->data_ptr<float>() : nullptr, lr.data_ptr<float>(), step_t.data_ptr<int>(),
+                        (float)beta1, (float)beta2, (float)eps, stream()),
+     "lin_wgrad_adam");
+}
+
+void lin_wgrad_ftrl(const Tensor& dy, const Tensor& x, const c10::optional<Tensor>& idx, const Tensor& w,
+                    const Tensor& z, const Tensor& n, const Tensor& w16, const Tensor& w16t,
+                    const c10::optional<Tensor>& bias, const c10::optional<Tensor>& bz,
+                    const c10::optional<Tensor>& bn, const Tensor& lr, double l1, double beta, double wd) {
+  const WgShape s = chk_wgrad("lin_wgrad_ftrl", dy, x, idx, w, w16, w16t, lr);
+  chk(z, at::kFloat, s.N * s.K, "z");
+  chk(n, at::kFloat, s.N * s.K, "n");
+  const bool hb = chk_bias2(bias, bz, bn, s.N, "bz", "bn");
+  ok(M_::lin_wgrad_ftrl(bp(dy), bp(x), idx_p(idx), (int)s.M, (int)s.N, (int)s.K, w.data_ptr<float>(),
+                        z.data_ptr<float>(), n.data_ptr<float>(), bp(w16), bp(w16t),
+                        hb ? bias->data_ptr<float>() : nullptr, hb ? bz->data_ptr<float>() : nullptr,
+                        hb ? bn->data_ptr<float>() : nullptr, lr.data_ptr<float>(), (float)l1, (float)beta, (float)wd,
+                        stream()),
+     "lin_wgrad_ftrl");
+}
+
 void xent_small(const Tensor& logits, const Tensor& y, const c10::optional<Tensor>& idx, const Tensor& dl,
-                int64_t C, const Tensor& stats) {
+                int64_t C, const Tensor& stats, const c10::optional<Tensor>& step_t) {
   TORCH_CHECK(logits.dim() == 2, "logits must be [M, ld]");
   const int64_t M = logits.size(0), ld = logits.size(1);
   TORCH_CHECK(C > 0 && C <= ld && ld <= 64, "xent_small: 0 < C <= ld <= 64");
@@ -84,8 +154,10 @@ void xent_small(const Tensor& logits, const Tensor& y, const c10::optional<Tenso
   chk_idx(idx, M);
   TORCH_CHECK(idx.has_value() || y.numel() == M, "labels must have one entry per row without a gather");
   TORCH_CHECK(stats.is_cuda() && stats.scalar_type() == at::kFloat && stats.numel() == 2, "stats: fp32[2]");
+  if (step_t.has_value()) chk_step_t(*step_t);
   ok(M_::xent_small(bp(logits), y.data_ptr<int64_t>(), idx.has_value() ? idx->data_ptr<int64_t>() : nullptr, bp(dl),
-                    (int)M, (int)C, (int)ld, stats.data_ptr<float>(), stream()),
+                    (int)M, (int)C, (int)ld, stats.data_ptr<float>(),
+                    step_t.has_value() ? step_t->data_ptr<int>() : nullptr, stream()),
      "xent_small");
 }
 
@@ -94,5 +166,10 @@ void xent_small(const Tensor& logits, const Tensor& y, const c10::optional<Tenso
 void register_mlp(py::module& m) {
   m.def("lin_fwd", &lin_fwd, "fused linear (+bias, +ReLU or ReLU-derivative mask), optional row gather");
   m.def("lin_wgrad_sgd", &lin_wgrad_sgd, "weight/bias gradient with fused SGD-momentum update");
-  m.def("xent_small", &xent_small, "softmax cross-entropy + gradient for a few classes");
+  m.def("lin_wgrad_adam", &lin_wgrad_adam, "weight/bias gradient with fused Adam update (t = step_t[0], 1-based)");
+  m.def("lin_wgrad_ftrl", &lin_wgrad_ftrl, "weight/bias gradient with fused FTRL-proximal update");
+  m.def("xent_small", &xent_small,
+        "softmax cross-entropy + gradient for a few classes; advances the int32 device counter step_t when given",
+        py::arg("logits"), py::arg("y"), py::arg("idx"), py::arg("dl"), py::arg("C"), py::arg("stats"),
+        py::arg("step_t") = py::none());
 }

@@ -17,10 +17,18 @@ device-resident dataset itself), a few-class cross-entropy that also emits the l
 gradient, two dgrad GEMMs with the ReLU-derivative mask in their epilogue, and three
 weight-gradient GEMMs that apply SGD with momentum to the fp32 masters (and refresh
 the bf16 weight / transposed-weight shadows) in their epilogue. ``--impl module`` is the
-``nn.Module`` + autocast + ``torch.optim.SGD`` path (CPU default, oracle).
+``nn.Module`` + autocast + ``torch.optim`` path (CPU default, oracle).
 
-Prints ``epoch=<e> loss=<l> Validation-accuracy=<a>`` per epoch (default StdOut
-collector format).
+The B1 search space (``--num-layers`` hidden layers of width ``--hidden``, ``--optimizer``
+sgd / adam / ftrl) runs on the same kernels with ``--impl hip``: 3L + 3 launches per step
+for L hidden layers, Adam and FTRL-proximal fused into the weight-gradient epilogue like
+SGD, Adam's step number kept in a device counter that the cross-entropy launch advances
+(so a replayed graph needs no host work). It needs ``--hidden`` to be a multiple of 8.
+``--impl auto`` still sends those flags to the module path; ``--unroll`` applies to the
+module path only.
+
+Prints ``epoch=<e> loss=<l> Validation-accuracy=<a> Train-accuracy=<t>`` per epoch
+(default StdOut collector format).
 """
 
 from __future__ import annotations
@@ -125,28 +133,47 @@ class MLP(torch.nn.Module):
         return self.fc3(F.relu(self.fc2(F.relu(self.fc1(x)))))
 
 
-class HipMLP:
-    """784 -> h -> h/2 -> 10 on the fused HIP kernels; parameters initialised from an
-    ``MLP`` module (same init as the module path). The output layer is padded to 16 rows
-    (zero weights, zero gradients) so every GEMM dimension is a multiple of 8."""
+_HIP_STATE = {"sgd": ("wm", None, "bm", None), "adam": ("m", "v", "bm", "bv"), "ftrl": ("z", "n", "bz", "bn")}
 
-    def __init__(self, ref: MLP, lr: float, momentum: float, dev):
+
+class HipMLP:
+    """An MLP on the fused HIP kernels: 784 -> h -> h/2 -> 10 from an ``MLP`` module, or 784 ->
+    ``hidden`` x ``num_layers`` -> 10 from a ``DeepMLP`` (same init as the module path), trained
+    with ``optimizer`` = sgd (momentum), adam (betas 0.9 / 0.999, eps 1e-8) or ftrl (``Ftrl``'s
+    defaults: lamda1 0.01, beta 1, no weight decay) - what the module path passes. The output
+    layer is padded to 16 rows (zero weights, zero gradients) so every GEMM dimension is a
+    multiple of 8. Each layer dict holds the fp32 master ``w`` / ``b``, the bf16 shadows ``w16`` /
+    ``w16t`` and the optimizer's state: ``wm`` / ``bm``, ``m`` / ``v`` / ``bm`` / ``bv`` or ``z`` /
+    ``n`` / ``bz`` / ``bn``. ``step_t`` is Adam's device step counter: 0 before the first step,
+    advanced by every ``train_step`` (eager or replayed) inside its cross-entropy launch."""
+
+    ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-8
+    FTRL_L1, FTRL_BETA, FTRL_WD = 0.01, 1.0, 0.0
+
+    def __init__(self, ref, lr: float, momentum: float, dev, optimizer: str = "sgd"):
         from ..ops.conv import kernels
 
         self.k = kernels()
         self.momentum = momentum
+        self.optimizer = optimizer
         self.lr = torch.full((1,), lr, device=dev, dtype=torch.float32)
+        self.step_t = torch.zeros(1, device=dev, dtype=torch.int32)
+        fcs = [ref.fc1, ref.fc2, ref.fc3] if isinstance(ref, MLP) else list(ref.hidden) + [ref.out]
         self.layers = []
-        for i, fc in enumerate((ref.fc1, ref.fc2, ref.fc3)):
+        for i, fc in enumerate(fcs):
             w = fc.weight.detach().float()
             b = fc.bias.detach().float()
-            if i == 2:
+            if i == len(fcs) - 1:
                 w = torch.cat([w, w.new_zeros(16 - w.shape[0], w.shape[1])])
                 b = torch.cat([b, b.new_zeros(16 - b.shape[0])])
             w = w.to(dev).contiguous()
             b = b.to(dev).contiguous()
-            self.layers.append({"w": w, "wm": torch.zeros_like(w), "w16": w.to(torch.bfloat16),
-                                "w16t": w.t().contiguous().to(torch.bfloat16), "b": b, "bm": torch.zeros_like(b)})
+            layer = {"w": w, "w16": w.to(torch.bfloat16), "w16t": w.t().contiguous().to(torch.bfloat16), "b": b}
+            ws0, ws1, bs0, bs1 = _HIP_STATE[optimizer]
+            layer[ws0], layer[bs0] = torch.zeros_like(w), torch.zeros_like(b)
+            if ws1 is not None:
+                layer[ws1], layer[bs1] = torch.zeros_like(w), torch.zeros_like(b)
+            self.layers.append(layer)
         self.stats = torch.zeros(2, device=dev, dtype=torch.float32)
 
     def forward(self, x, idx=None, save=False):
@@ -156,29 +183,35 @@ class HipMLP:
         h = x
         for i, l in enumerate(L):
             y = torch.empty((M, l["w"].shape[0]), device=x.device, dtype=torch.bfloat16)
-            k.lin_fwd(h, idx if i == 0 else None, l["w16"], l["b"], None, y, i < 2)
+            k.lin_fwd(h, idx if i == 0 else None, l["w16"], l["b"], None, y, i < len(L) - 1)
             acts.append(y)
             h = y
         return acts if save else acts[-1]
 
     def train_step(self, x, y, idx):
         k, L = self.k, self.layers
-        h1, h2, lg = self.forward(x, idx, save=True)
-        M = idx.numel()
-        dl = torch.empty_like(lg)
-        k.xent_small(lg, y, idx, dl, 10, self.stats)
-        dh2 = torch.empty_like(h2)
-        k.lin_fwd(dl, None, L[2]["w16t"], None, h2, dh2, False)  # dgrad before the update of W3
-        self._sgd(dl, h2, None, L[2])
-        dh1 = torch.empty_like(h1)
-        k.lin_fwd(dh2, None, L[1]["w16t"], None, h1, dh1, False)
-        self._sgd(dh2, h1, None, L[1])
-        self._sgd(dh1, x, idx, L[0])
+        acts = self.forward(x, idx, save=True)
+        dy = torch.empty_like(acts[-1])
+        k.xent_small(acts[-1], y, idx, dy, 10, self.stats, self.step_t if self.optimizer == "adam" else None)
+        for i in range(len(L) - 1, 0, -1):
+            dh = torch.empty_like(acts[i - 1])
+            k.lin_fwd(dy, None, L[i]["w16t"], None, acts[i - 1], dh, False)  # dgrad before the update of W_i
+            self._update(dy, acts[i - 1], None, L[i])
+            dy = dh
+        self._update(dy, x, idx, L[0])
         return self.stats
 
-    def _sgd(self, dy, x, idx, l):
-        self.k.lin_wgrad_sgd(dy, x, idx, l["w"], l["wm"], l["w16"], l["w16t"], l["b"], l["bm"], self.lr,
-                             self.momentum)
+    def _update(self, dy, x, idx, l):
+        k = self.k
+        if self.optimizer == "adam":
+            k.lin_wgrad_adam(dy, x, idx, l["w"], l["m"], l["v"], l["w16"], l["w16t"], l["b"], l["bm"], l["bv"],
+                             self.lr, self.step_t, self.ADAM_BETAS[0], self.ADAM_BETAS[1], self.ADAM_EPS)
+        elif self.optimizer == "ftrl":
+            k.lin_wgrad_ftrl(dy, x, idx, l["w"], l["z"], l["n"], l["w16"], l["w16t"], l["b"], l["bz"], l["bn"],
+                             self.lr, self.FTRL_L1, self.FTRL_BETA, self.FTRL_WD)
+        else:
+            k.lin_wgrad_sgd(dy, x, idx, l["w"], l["wm"], l["w16"], l["w16t"], l["b"], l["bm"], self.lr,
+                            self.momentum)
 
 
 def main(argv=None):
@@ -186,6 +219,9 @@ def main(argv=None):
     phase("module", _T_MODULE)
     phase("torch", _T_TORCH)
     args = parse_args(argv if argv is not None else [])
+    if args.impl == "hip" and args.hidden % 8:
+        raise SystemExit("--impl hip needs --hidden to be a multiple of 8 (got %d): the fused kernels read "
+                         "16-byte rows" % args.hidden)
     dev = device()
     if dev.type == "cuda":
         torch.zeros(1, device=dev).add_(1)
@@ -200,8 +236,6 @@ def main(argv=None):
     model = (DeepMLP(args.hidden, args.num_layers or 2) if custom else MLP(args.hidden)).to(dev)
     impl = args.impl if args.impl != "auto" else ("hip" if dev.type == "cuda" and not custom else "module")
     if impl == "hip":
-        if custom:
-            raise SystemExit("--impl hip runs the 784-h-h/2-10 net with SGD only")
         return _main_hip(args, dev, model, tx, ty, vx, vy)
     if args.optimizer == "adam":
         opt = torch.optim.Adam(model.parameters(), lr=args.lr, capturable=dev.type == "cuda")
@@ -298,13 +332,14 @@ def main(argv=None):
 
 
 def _main_hip(args, dev, model, tx, ty, vx, vy):
-    net = HipMLP(model, args.lr, args.momentum, dev)
+    net = HipMLP(model, args.lr, args.momentum, dev, args.optimizer)
     txb, vxb = tx.to(torch.bfloat16).contiguous(), vx.to(torch.bfloat16).contiguous()
     bs = max(1, min(args.batch_size, args.num_train))
     steps = args.num_train // bs
     idx = torch.zeros(bs, dtype=torch.long, device=dev)
     step = CapturedStep(lambda: net.train_step(txb, ty, idx), enabled=bool(args.capture))
     gen = torch.Generator(device=dev).manual_seed(args.seed)
+    phase("model")
     timer = Timer()
     acc = 0.0
     for epoch in range(args.epochs):
@@ -313,11 +348,18 @@ def _main_hip(args, dev, model, tx, ty, vx, vy):
         for s in range(steps):
             idx.copy_(perm[s])
             step()
+            if epoch == 0 and s == step.warmup:
+                phase("captured")  # warm-up steps + graph capture + first replay issued
         with torch.no_grad():
             acc = float((net.forward(vxb)[:, :10].argmax(1) == vy).float().mean())
-        loss = float(net.stats[0]) / max(steps, 1)
-        report(epoch=epoch, loss=loss if math.isfinite(loss) else float("nan"), **{"Validation-accuracy": acc})
+        stats = net.stats.tolist()
+        loss = stats[0] / max(steps, 1)
+        report(epoch=epoch, loss=loss if math.isfinite(loss) else float("nan"),
+               **{"Validation-accuracy": acc, "Train-accuracy": stats[1] / max(steps * bs, 1)})
+        if epoch == 0:
+            phase("first_metric")
     report(**{"train_seconds": timer.elapsed()})
+    phase("trained")
     return acc
 
 
