@@ -504,48 +504,112 @@ void dw_bwd_fill(std::vector<py::tuple>& calls, DwBwdBatch& bt, const int64_t* K
   }
 }
 
-// stride-1 and stride-2 pool backward of a node in one launch:
-// (ga|None, gm|None, x, dout_id|None, w|None, id_idx, gx, amax|None, overwrite, S[, extras]) per entry
+// one edge's share of a pooled op's BN backward: (S1|None, S2|None, w, widx, rep, rstride, rvar|None);
+// training reads the S1 / S2 replicas, eval the edge's own running variance
+static PoolGradPart make_pool_part(const py::tuple& t, int C, bool eval) {
+  PoolGradPart g{};
+  TORCH_CHECK(t.size() == 7, "pool grad part has 7 fields");
+  OptT s1 = t[0].cast<OptT>(), s2 = t[1].cast<OptT>(), rvar = t[6].cast<OptT>();
+  Tensor w = t[2].cast<Tensor>();
+  check_f32(w, "w");
+  g.w = w.data_ptr<float>();
+  g.widx = t[3].cast<int>();
+  TORCH_CHECK(g.widx >= 0 && g.widx < w.numel(), "pool_bwd: weight index out of range");
+  g.rep = t[4].cast<int>();
+  g.rstride = t[5].cast<int>();
+  TORCH_CHECK(g.rep >= 1 && g.rep <= kRep, "replicas");
+  if (eval) {
+    TORCH_CHECK(rvar.has_value() && rvar->defined(), "eval-mode pool backward needs the edge's running variance");
+    check_f32(*rvar, "rvar");
+    TORCH_CHECK(rvar->numel() == C, "rvar [C]");
+    g.rvar = rvar->data_ptr<float>();
+    return g;
+  }
+  TORCH_CHECK(s1.has_value() && s1->defined() && s2.has_value() && s2->defined(),
+              "training-mode BN backward needs S1/S2 reductions");
+  for (const OptT* sv : {&s1, &s2})
+    TORCH_CHECK((*sv)->scalar_type() == at::kDouble && (*sv)->is_cuda() &&
+                    storage_doubles_after(**sv) >= (int64_t)(g.rep - 1) * g.rstride + C,
+                "S1/S2 replicas exceed their buffer");
+  g.S1 = s1->data_ptr<double>();
+  g.S2 = s2->data_ptr<double>();
+  return g;
+}
+
+// stride-1 and stride-2 pool backward of several cell states in one launch, per entry (= state):
+// (zavg|None, zmax|None, bn_avg|None, bn_max|None, amax|None, x, gx, overwrite, S, sources), each of the
+// 1..kMaxShare sources (= edges reading the state) (dout, avg part|None, max part|None, w_id|None, id_idx, extras)
 void pool_bwd_multi(std::vector<py::tuple> calls) {
   check_batch<PoolBwdBatch>(calls);
   PoolBwdBatch bt{};
   bt.n = calls.size();
   for (int i = 0; i < bt.n; ++i) {
     const py::tuple& t = calls[i];
-    const int64_t S = t[9].cast<int64_t>();
+    TORCH_CHECK(t.size() == 10, "pool_bwd entry has 10 fields");
+    const int64_t S = t[8].cast<int64_t>();
     TORCH_CHECK(S == 1 || S == 2, "pool stride must be 1 or 2");
-    bt.e[i].S = (int)S;
-    auto ga = t[0].cast<c10::optional<py::tuple>>(), gm = t[1].cast<c10::optional<py::tuple>>();
-    Tensor x = t[2].cast<Tensor>();
-    OptT dout_id = t[3].cast<OptT>(), w = t[4].cast<OptT>();
-    const int id_idx = t[5].cast<int>();
-    Tensor gx = t[6].cast<Tensor>();
-    OptT amax = t[7].cast<OptT>();
+    OptT za = t[0].cast<OptT>(), zm = t[1].cast<OptT>(), amax = t[4].cast<OptT>();
+    auto bna = t[2].cast<c10::optional<py::tuple>>(), bnm = t[3].cast<c10::optional<py::tuple>>();
+    Tensor x = t[5].cast<Tensor>(), gx = t[6].cast<Tensor>();
     check_f32(x, "x"); check_f32(gx, "gx");
+    TORCH_CHECK(x.dim() == 4, "x must be NCHW");
     PoolBwdArgs& a = bt.e[i];
+    a.S = (int)S;
     a.N = x.size(0); a.C = x.size(1); a.H = x.size(2); a.W = x.size(3);
     a.Ho = (a.H - 1) / S + 1; a.Wo = (a.W - 1) / S + 1;
     TORCH_CHECK(a.Ho * a.Wo <= 8192, "pool_bwd stages one output plane in LDS (Ho*Wo <= 8192)");
     TORCH_CHECK(gx.sizes() == x.sizes(), "gx shape");
-    TORCH_CHECK(!gm.has_value() || (amax.has_value() && amax->defined() && amax->scalar_type() == at::kByte &&
-                                    amax->numel() == (int64_t)a.N * a.C * a.Ho * a.Wo),
-                "max-pool backward needs the uint8 argmax from pool_fwd");
-    if (amax.has_value() && amax->defined()) a.amax = amax->data_ptr<uint8_t>();
-    if (ga.has_value()) a.ga = make_gs(*ga, a.C);
-    if (gm.has_value()) a.gm = make_gs(*gm, a.C);
-    a.x = x.data_ptr<float>(); a.dout_id = ptr_or_null<float>(dout_id); a.w = ptr_or_null<float>(w);
-    if (a.dout_id) TORCH_CHECK(dout_id->sizes() == x.sizes(), "identity gradient shape");
-    a.id_idx = id_idx; a.gx = gx.data_ptr<float>();
-    a.overwrite = t[8].cast<bool>();
-    if (t.size() > 10) {  // (..., S, extras): other input-gradient parts to sum in
-      auto ex = t[10].cast<std::vector<Tensor>>();
-      TORCH_CHECK(ex.size() <= 4, "pool_bwd: at most 4 extra gradient parts");
-      a.nextra = ex.size();
+    const int64_t onumel = (int64_t)a.N * a.C * a.Ho * a.Wo;
+    const bool has_a = za.has_value() && za->defined(), has_m = zm.has_value() && zm->defined();
+    if (has_a) {
+      check_z(*za, "zavg");
+      TORCH_CHECK(za->numel() == onumel && bna.has_value(), "avg-pool backward needs zavg [N][C][Ho][Wo] and its BN");
+      a.za = zptr(*za);
+      a.bna = make_bn(*bna, a.C);
+    }
+    if (has_m) {
+      check_z(*zm, "zmax");
+      TORCH_CHECK(zm->numel() == onumel && bnm.has_value(), "max-pool backward needs zmax [N][C][Ho][Wo] and its BN");
+      TORCH_CHECK(amax.has_value() && amax->defined() && amax->is_cuda() && amax->scalar_type() == at::kByte &&
+                      amax->is_contiguous() && amax->numel() == onumel,
+                  "max-pool backward needs the uint8 argmax from pool_fwd");
+      a.zm = zptr(*zm);
+      a.bnm = make_bn(*bnm, a.C);
+      a.amax = amax->data_ptr<uint8_t>();
+    }
+    a.gx = gx.data_ptr<float>();
+    a.overwrite = t[7].cast<bool>();
+    auto srcs = t[9].cast<std::vector<py::tuple>>();
+    TORCH_CHECK(!srcs.empty() && (int)srcs.size() <= kMaxShare, "pool_bwd: 1..", kMaxShare, " sources per entry");
+    a.nsrc = srcs.size();
+    for (int e = 0; e < a.nsrc; ++e) {
+      const py::tuple& u = srcs[e];
+      TORCH_CHECK(u.size() == 6, "pool_bwd source has 6 fields");
+      PoolBwdSrc& sr = a.src[e];
+      Tensor dout = u[0].cast<Tensor>();
+      check_f32(dout, "dout");
+      TORCH_CHECK(dout.numel() == onumel, "dout must be [N][C][Ho][Wo]");
+      sr.dout = dout.data_ptr<float>();
+      auto pa = u[1].cast<c10::optional<py::tuple>>(), pm = u[2].cast<c10::optional<py::tuple>>();
+      TORCH_CHECK((!pa.has_value() || has_a) && (!pm.has_value() || has_m), "pool_bwd: a source's pool lacks its z");
+      if (pa.has_value()) sr.a = make_pool_part(*pa, a.C, a.bna.eval);
+      if (pm.has_value()) sr.m = make_pool_part(*pm, a.C, a.bnm.eval);
+      OptT w_id = u[3].cast<OptT>();
+      sr.id_idx = u[4].cast<int>();
+      if (w_id.has_value() && w_id->defined() && sr.id_idx >= 0) {
+        check_f32(*w_id, "w");
+        TORCH_CHECK(S == 1, "the identity skip is stride 1");
+        TORCH_CHECK(sr.id_idx < w_id->numel(), "id_idx out of range");
+        sr.w_id = w_id->data_ptr<float>();
+      }
+      auto ex = u[5].cast<std::vector<Tensor>>();
+      TORCH_CHECK(ex.size() <= 4, "pool_bwd: at most 4 extra gradient parts per source");
+      sr.nextra = ex.size();
       for (size_t j = 0; j < ex.size(); ++j) {
         check_f32(ex[j], "extra");
         TORCH_CHECK(ex[j].sizes() == gx.sizes(), "extra gradient part shape");
         TORCH_CHECK(ex[j].data_ptr() != gx.data_ptr(), "extra part aliases gx");
-        a.extra[j] = ex[j].data_ptr<float>();
+        sr.extra[j] = ex[j].data_ptr<float>();
       }
     }
     SAME_SHAPE(bt, N); SAME_SHAPE(bt, C);
@@ -620,6 +684,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fold_rows", &fold_rows);
   m.def("fold_f64", &fold_f64);
   m.attr("REP") = kRep;
+  m.attr("POOL_SHARE") = kMaxShare;
   m.attr("ZBF16") = kZbf16;  // per-op intermediates stored as bf16 (the _hipkern_zbf16 variant)
   m.def("max_blocks", &max_blocks);
   m.def("dwpw_split_path", [](int64_t C) { return dwpw_split_path((int)C); });  // such stages need d

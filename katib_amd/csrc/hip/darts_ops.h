@@ -160,10 +160,32 @@ struct FoldF64Args {  // per segment: p[i] = sum_{r < kRep} p[r*rstride + i]; re
   double* p[kMaxSeg]; int n[kMaxSeg]; int rstride[kMaxSeg]; int nseg; int total;
 };
 
+// pool_bwd forms the gradient of ONE cell state from every edge that reads it with the same stride:
+// the pooled tensors, their batch statistics and the argmax are the same for all of them (pooling
+// has no parameters, its BN no affine part), so they are per entry; what differs per edge - its
+// dout, BN-backward sums, softmax weights, running statistics (eval), identity skip and conv
+// input-gradient parts - comes as up to kMaxShare sources that the kernel sums while staging.
+constexpr int kMaxShare = 4;
+struct PoolGradPart {       // one edge's share of a pooled op's BN backward (on: w != nullptr)
+  const double* S1;         // [C] sum g, [C] sum g * zhat (replica r at + r*rstride); eval: unused
+  const double* S2;
+  const float* w;           // the edge's softmax weights
+  const float* rvar;        // eval: the edge's own running variance
+  int widx, rep, rstride;
+};
+struct PoolBwdSrc {
+  const float* dout;        // the consuming node's output gradient
+  PoolGradPart a, m;        // avg / max pool of this edge
+  const float* w_id;        // identity skip: gx += w_id[id_idx] * dout (nullptr: none)
+  int id_idx;
+  const float* extra[4]; int nextra;  // the edge's other input-gradient parts (conv backward)
+};
 struct PoolBwdArgs {
-  GradSrc ga; GradSrc gm; const float* x; const float* dout_id; const float* w; int id_idx; float* gx;
+  const zt* za; const zt* zm;  // the state's pooled tensors (nullptr: no source has that pool)
+  BNRef bna, bnm;              // their batch statistics (eval: every source normalises with its own rvar)
   const unsigned char* amax;
-  const float* extra[4]; int nextra;  // other input-gradient parts of this edge summed in (conv backward)
+  float* gx;
+  PoolBwdSrc src[kMaxShare]; int nsrc;
   int overwrite;  // gx = result instead of +=
   int N, C, H, W, Ho, Wo;
   int S;          // pool_bwd_multi_kernel: per-entry stride

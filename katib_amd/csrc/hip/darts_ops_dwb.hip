@@ -155,41 +155,73 @@ __global__ void __launch_bounds__(256) dw_bwd_kernel(DwBwdBatch bt) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// pool_bwd: gx += avg^T(dz_avg) + max^T(dz_max) + wid * dout (identity skip), per (n,c) plane
+// pool_bwd: the gradient of one cell state from every edge that reads it (PoolBwdArgs), per (n,c)
+// plane: gx (+)= avg^T(sum_e dz_avg_e) + max^T(sum_e dz_max_e) + sum_e (wid_e * dout_e + conv parts_e)
 // ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float wave_uniform(float v) {
+  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
+}
+
+// the entry's sources read where they are used, through the kernel-argument segment: copied into
+// registers with the rest of the entry they are ~100 scalar registers, all live from the first
+// instruction on, and most of them spill
+typedef const PoolBwdSrc __attribute__((address_space(4))) * PoolSrcPtr;
+
 template <int S, bool V4 = false>
-__device__ __forceinline__ void pool_bwd_body(const PoolBwdArgs& a, const int bx) {
+__device__ __forceinline__ void pool_bwd_body(const PoolBwdArgs& a, PoolSrcPtr src, const int bx) {
   const int C = a.C, H = a.H, W = a.W, Ho = a.Ho, Wo = a.Wo, HWo = Ho * Wo;
   const int nc = bx, c = nc % C;
   const size_t ob = (size_t)nc * HWo;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  float* sGa = smem;                                          // [HWo] dz_avg / window count
-  float* sGm = smem + HWo;                                    // [HWo] dz_max
+  float* sGa = smem;                                          // [HWo] sum_e dz_avg / window count
+  float* sGm = smem + HWo;                                    // [HWo] sum_e dz_max
   unsigned char* sArg = (unsigned char*)(smem + 2 * HWo);     // [HWo] argmax tap
-  // the plane's BN coefficients: four threads each sum one pair over the replicas
-  __shared__ float sCo[8];
+  // the plane's coefficients: (mean, 1 / std) of both pooled tensors, then per source the two
+  // BN-backward means of its avg pool and of its max pool
+  __shared__ float sCo[4 + 4 * kMaxShare];
   KSTAMP(0);
-  // all four replica pair-sums in ONE memory round trip: wave 0's 16-lane groups take the avg
-  // pool's BN statistics, the max pool's, and the two BN-backward sums (S1, S2) each - folded
-  // (rep 1) or not (rep kRep: two loads per lane). One thread per BN walking kRep replicas in
-  // rounds of 8 was four dependent round trips (~2.8 us of a ~10 us workgroup, phase stamps r06)
-  if (threadIdx.x < 64) {
+  // every replica pair-sum in ONE memory round trip: 16-lane groups take the avg pool's BN
+  // statistics, the max pool's, and per source the BN-backward sums (S1, S2) of its avg and of its
+  // max pool - folded (rep 1) or not (rep kRep: two loads per lane). One thread per BN walking kRep
+  // replicas in rounds of 8 was four dependent round trips (~2.8 us of a ~10 us workgroup, phase
+  // stamps r06). The sources are picked with constant indices: a dynamic index into the argument
+  // copy would send it to scratch
+  if (threadIdx.x < 16 * (2 + 2 * kMaxShare)) {
     const int grp = threadIdx.x >> 4, j = threadIdx.x & 15;
-    const GradSrc& gs = grp & 1 ? a.gm : a.ga;
-    const bool on = gs.z != nullptr, stats = grp < 2;
-    const BNRef& b = gs.bn;
-    double s = 0.0, s2 = 0.0;
-    if (on && stats && !b.eval) {
-      for (int r = j; r < b.rep; r += 16) {
-        s += b.sums[(size_t)r * b.rstride + c];
-        s2 += b.sums[(size_t)r * b.rstride + b.C + c];
+    const bool stats = grp < 2;
+    const BNRef& b = grp & 1 ? a.bnm : a.bna;
+    const bool on = (grp & 1 ? a.zm != nullptr : a.za != nullptr);
+    const double* p1 = nullptr;
+    size_t off2 = 0;
+    int rep = 0, rs = 0;
+#pragma unroll
+    for (int e = 0; e < kMaxShare; ++e) {
+      if (e < a.nsrc && (grp >> 1) == e + 1) {
+        const float* gw = grp & 1 ? src[e].m.w : src[e].a.w;
+        const double* g1 = grp & 1 ? src[e].m.S1 : src[e].a.S1;
+        const double* g2 = grp & 1 ? src[e].m.S2 : src[e].a.S2;
+        const int grep = grp & 1 ? src[e].m.rep : src[e].a.rep;
+        const int grs = grp & 1 ? src[e].m.rstride : src[e].a.rstride;
+        if (gw && g1) {
+          p1 = g1;
+          off2 = g2 - g1;
+          rep = grep;
+          rs = grep == 1 ? 0 : grs;
+        }
       }
-    } else if (on && !stats && !gs.eval) {
-      const int rep = gs.rep, rs = gs.rep == 1 ? 0 : gs.rstride;
-      const size_t off2 = gs.S2 - gs.S1;
+    }
+    double s = 0.0, s2 = 0.0;
+    if (stats) {
+      if (on && !b.eval) {
+        for (int r = j; r < b.rep; r += 16) {
+          s += b.sums[(size_t)r * b.rstride + c];
+          s2 += b.sums[(size_t)r * b.rstride + b.C + c];
+        }
+      }
+    } else if (p1) {
       for (int r = j; r < rep; r += 16) {
-        s += gs.S1[(size_t)r * rs + c];
-        s2 += gs.S1[(size_t)r * rs + off2 + c];
+        s += p1[(size_t)r * rs + c];
+        s2 += p1[(size_t)r * rs + off2 + c];
       }
     }
 #pragma unroll
@@ -198,14 +230,11 @@ __device__ __forceinline__ void pool_bwd_body(const PoolBwdArgs& a, const int bx
       s2 += __shfl_xor(s2, o, 64);
     }
     if (j == 0) {
-      float* o = sCo + 4 * (grp & 1) + (stats ? 0 : 2);
-      if (!on) {
-        o[0] = 0.f;
-        o[1] = stats ? 1.f : 0.f;
-      } else if (stats) {
-        if (b.eval) {
-          o[0] = b.rmean[c];
-          o[1] = rsqrtf(b.rvar[c] + b.eps);
+      float* o = sCo + 2 * grp;  // stats: 0 / 2; source e: 4 + 4 e (avg), 4 + 4 e + 2 (max)
+      if (stats) {
+        if (!on || b.eval) {  // eval: every source scales by its own running variance; zhat is unused
+          o[0] = 0.f;
+          o[1] = 1.f;
         } else {  // as bn_moments / bn_coeffs
           const double m = s * (double)b.inv_count;
           double v = s2 * (double)b.inv_count - m * m;
@@ -213,58 +242,93 @@ __device__ __forceinline__ void pool_bwd_body(const PoolBwdArgs& a, const int bx
           o[0] = (float)m;
           o[1] = rsqrtf((float)v + b.eps);
         }
-      } else {  // as gs_means
-        o[0] = gs.eval ? 0.f : (float)(s * (double)gs.bn.inv_count);
-        o[1] = gs.eval ? 0.f : (float)(s2 * (double)gs.bn.inv_count);
+      } else {  // as gs_means (no sums - eval, or the edge lacks this pool: 0)
+        o[0] = (float)(s * (double)b.inv_count);
+        o[1] = (float)(s2 * (double)b.inv_count);
       }
     }
   }
   __syncthreads();
   KSTAMP(1);
-  const float ma = sCo[0], ia = sCo[1], a1 = a.ga.z ? sCo[2] : 0.f, a2 = a.ga.z ? sCo[3] : 0.f;
-  const float mm = sCo[4], im = sCo[5], m1 = a.gm.z ? sCo[6] : 0.f, m2 = a.gm.z ? sCo[7] : 0.f;
-  const float wa = a.ga.w ? a.ga.w[a.ga.widx] : 0.f;
-  const float wm = a.gm.w ? a.gm.w[a.gm.widx] : 0.f;
-  const float wid = (a.w && a.id_idx >= 0) ? a.w[a.id_idx] : 0.f;
+  // (the same values in every lane: kept in scalar registers)
+  const float ma = wave_uniform(sCo[0]), ia = wave_uniform(sCo[1]), mm = wave_uniform(sCo[2]), im = wave_uniform(sCo[3]);
+  // per source: weight * 1 / std of each pool (0: the edge lacks it), its BN-backward means, its
+  // identity weight
+  float ca[kMaxShare], a1[kMaxShare], a2[kMaxShare], cm[kMaxShare], m1[kMaxShare], m2[kMaxShare], wid[kMaxShare];
+#pragma unroll
+  for (int e = 0; e < kMaxShare; ++e) {
+    ca[e] = cm[e] = wid[e] = 0.f;
+    a1[e] = wave_uniform(sCo[4 + 4 * e]);
+    a2[e] = wave_uniform(sCo[5 + 4 * e]);
+    m1[e] = wave_uniform(sCo[6 + 4 * e]);
+    m2[e] = wave_uniform(sCo[7 + 4 * e]);
+    if (e < a.nsrc) {
+      if (a.za && src[e].a.w)
+        ca[e] = src[e].a.w[src[e].a.widx] * (a.bna.eval ? rsqrtf(src[e].a.rvar[c] + a.bna.eps) : ia);
+      if (a.zm && src[e].m.w)
+        cm[e] = src[e].m.w[src[e].m.widx] * (a.bnm.eval ? rsqrtf(src[e].m.rvar[c] + a.bnm.eps) : im);
+      if (src[e].w_id) wid[e] = src[e].w_id[src[e].id_idx];
+    }
+  }
   if constexpr (V4) {
     // 4 consecutive outputs / input pixels per thread: every operand one 16-byte (amax: 4-byte)
     // access instead of four 4-byte ones - a quarter of the memory requests in flight for the
     // same bytes (HWo, H*W % 4 == 0 and every operand 16-byte aligned: host-checked)
     typedef float f4 __attribute__((ext_vector_type(4)));
-    const float* gsrc = a.ga.z ? a.ga.g : a.gm.g;  // both pools read the edge's dout
     for (int o4 = threadIdx.x * 4; o4 < HWo; o4 += 1024) {
-      const f4 g = *reinterpret_cast<const f4*>(gsrc + ob + o4);
-      if (a.ga.z) {
-        const f4 z = zld4(a.ga.z + ob + o4);
-        const f4 d = wa * ia * (g - a1 - ((z - ma) * ia) * a2);
+      // every load of the pass issued before the first use (they sit behind wave-uniform tests, and
+      // a load consumed inside its own test is one memory round trip per test); then zhat once per
+      // pixel and every source's BN backward of both pools summed (a source without that pool: c = 0)
+      f4 za4 = {0.f, 0.f, 0.f, 0.f}, zm4 = {0.f, 0.f, 0.f, 0.f}, gd[kMaxShare];
+      unsigned am4 = 0xffffffffu;
+      if (a.za) za4 = zld4(a.za + ob + o4);
+      if (a.zm) {
+        zm4 = zld4(a.zm + ob + o4);
+        am4 = *reinterpret_cast<const unsigned*>(a.amax + ob + o4);
+      }
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const int o = o4 + t, oy = o / Wo, ox = o - oy * Wo;
-          const int y0 = max(oy * S - 1, 0), y1 = min(oy * S + 1, H - 1);
-          const int x0 = max(ox * S - 1, 0), x1 = min(ox * S + 1, W - 1);
-          sGa[o] = d[t] / (float)((y1 - y0 + 1) * (x1 - x0 + 1));
-        }
-      } else {
-        *reinterpret_cast<f4*>(sGa + o4) = f4{0.f, 0.f, 0.f, 0.f};
+      for (int e = 0; e < kMaxShare; ++e) {
+        gd[e] = f4{0.f, 0.f, 0.f, 0.f};
+        if (e < a.nsrc && ((a.za && src[e].a.w) || (a.zm && src[e].m.w)))
+          gd[e] = *reinterpret_cast<const f4*>(src[e].dout + ob + o4);
       }
-      if (a.gm.z) {
-        const f4 z = zld4(a.gm.z + ob + o4);
-        *reinterpret_cast<f4*>(sGm + o4) = wm * im * (g - m1 - ((z - mm) * im) * m2);
-        *reinterpret_cast<unsigned*>(sArg + o4) = *reinterpret_cast<const unsigned*>(a.amax + ob + o4);
-      } else {
-        *reinterpret_cast<f4*>(sGm + o4) = f4{0.f, 0.f, 0.f, 0.f};
-        *reinterpret_cast<unsigned*>(sArg + o4) = 0xffffffffu;
+      const f4 zha = (za4 - ma) * ia, zhm = (zm4 - mm) * im;
+      f4 da = {0.f, 0.f, 0.f, 0.f}, dm = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int e = 0; e < kMaxShare; ++e) {
+        da += ca[e] * (gd[e] - a1[e] - zha * a2[e]);
+        dm += cm[e] * (gd[e] - m1[e] - zhm * m2[e]);
       }
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const int o = o4 + t, oy = o / Wo, ox = o - oy * Wo;
+        const int y0 = max(oy * S - 1, 0), y1 = min(oy * S + 1, H - 1);
+        const int x0 = max(ox * S - 1, 0), x1 = min(ox * S + 1, W - 1);
+        sGa[o] = da[t] / (float)((y1 - y0 + 1) * (x1 - x0 + 1));
+      }
+      *reinterpret_cast<f4*>(sGm + o4) = dm;
+      *reinterpret_cast<unsigned*>(sArg + o4) = am4;
     }
     __syncthreads();
     KSTAMP(2);
     const size_t pb = (size_t)nc * H * W;
     for (int q4 = threadIdx.x * 4; q4 < H * W; q4 += 1024) {
       f4 g = {0.f, 0.f, 0.f, 0.f};
-      if (a.dout_id) g = wid * *reinterpret_cast<const f4*>(a.dout_id + pb + q4);
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (j < a.nextra) g += *reinterpret_cast<const f4*>(a.extra[j] + pb + q4);
+      for (int e = 0; e < kMaxShare; ++e) {  // every source's identity skip and conv input-gradient parts:
+        if (e < a.nsrc) {                    // a source's loads all issued before the first is used
+          f4 dv = {0.f, 0.f, 0.f, 0.f}, xv[4];
+          if (src[e].w_id) dv = *reinterpret_cast<const f4*>(src[e].dout + pb + q4);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            xv[j] = f4{0.f, 0.f, 0.f, 0.f};
+            if (j < src[e].nextra) xv[j] = *reinterpret_cast<const f4*>(src[e].extra[j] + pb + q4);
+          }
+          g += wid[e] * dv;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) g += xv[j];
+        }
+      }
       const int iy = q4 / W, ix0 = q4 - iy * W;  // 4 pixels of one row (W % 4 == 0)
       if constexpr (S == 1) {
         // stride 1: the quad's 3 x 6 window of outputs (rows iy - 1 .. iy + 1, columns ix0 - 1 ..
@@ -375,20 +439,22 @@ __device__ __forceinline__ void pool_bwd_body(const PoolBwdArgs& a, const int bx
   }
   for (int o = threadIdx.x; o < HWo; o += 256) {
     int oy = o / Wo, ox = o % Wo;
-    if (a.ga.z) {
-      int y0 = max(oy * S - 1, 0), y1 = min(oy * S + 1, H - 1);
-      int x0 = max(ox * S - 1, 0), x1 = min(ox * S + 1, W - 1);
-      sGa[o] = bn_bwd_val(a.ga, ob + o, ma, ia, wa, a1, a2) / (float)((y1 - y0 + 1) * (x1 - x0 + 1));
-    } else {
-      sGa[o] = 0.f;
+    const float zha = a.za ? (z2f(a.za[ob + o]) - ma) * ia : 0.f;
+    const float zhm = a.zm ? (z2f(a.zm[ob + o]) - mm) * im : 0.f;
+    float da = 0.f, dm = 0.f;
+#pragma unroll
+    for (int e = 0; e < kMaxShare; ++e) {
+      if (e < a.nsrc && ((a.za && src[e].a.w) || (a.zm && src[e].m.w))) {
+        const float g = src[e].dout[ob + o];
+        if (a.za && src[e].a.w) da += ca[e] * (g - a1[e] - zha * a2[e]);
+        if (a.zm && src[e].m.w) dm += cm[e] * (g - m1[e] - zhm * m2[e]);
+      }
     }
-    if (a.gm.z) {
-      sGm[o] = bn_bwd_val(a.gm, ob + o, mm, im, wm, m1, m2);
-      sArg[o] = a.amax[ob + o];
-    } else {
-      sGm[o] = 0.f;
-      sArg[o] = 255;
-    }
+    int y0 = max(oy * S - 1, 0), y1 = min(oy * S + 1, H - 1);
+    int x0 = max(ox * S - 1, 0), x1 = min(ox * S + 1, W - 1);
+    sGa[o] = da / (float)((y1 - y0 + 1) * (x1 - x0 + 1));
+    sGm[o] = dm;
+    sArg[o] = a.zm ? a.amax[ob + o] : 255;
   }
   __syncthreads();
   for (int q = threadIdx.x; q < H * W; q += 256) {
@@ -405,22 +471,30 @@ __device__ __forceinline__ void pool_bwd_body(const PoolBwdArgs& a, const int bx
         if (sArg[o] == tap) g += sGm[o];
       }
     }
-    if (a.dout_id) g += wid * a.dout_id[(size_t)nc * H * W + q];
 #pragma unroll
-    for (int j = 0; j < 4; ++j)  // the node's conv input grads (constant indices: a dynamic index into
-      if (j < a.nextra) g += a.extra[j][(size_t)nc * H * W + q];  // the argument copy sends it to scratch)
+    for (int e = 0; e < kMaxShare; ++e) {  // identity skips and conv input grads (constant indices: a
+      if (e < a.nsrc) {                    // dynamic index into the argument copy sends it to scratch)
+        if (src[e].w_id) g += wid[e] * src[e].dout[(size_t)nc * H * W + q];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (j < src[e].nextra) g += src[e].extra[j][(size_t)nc * H * W + q];
+      }
+    }
     if (a.overwrite) a.gx[(size_t)nc * H * W + q] = g;
     else a.gx[(size_t)nc * H * W + q] += g;
   }
 }
 
-// stride-1 and stride-2 pool backward of a node in one launch (different edges: different gx)
+// stride-1 and stride-2 pool backward of several cell states in one launch (different states: different gx)
 template <bool V4>
 __global__ void __launch_bounds__(256) pool_bwd_multi_kernel(PoolBwdBatch bt) {
   const PoolBwdArgs a = bt.e[blockIdx.y];  // copy: see dwpw_plane_multi_kernel
   if ((int)blockIdx.x >= a.N * a.C) return;
-  if (a.S == 1) pool_bwd_body<1, V4>(a, blockIdx.x);
-  else pool_bwd_body<2, V4>(a, blockIdx.x);
+  // (bt is the kernel's only argument: it starts the kernel-argument segment)
+  typedef const PoolBwdBatch __attribute__((address_space(4))) * BatchPtr;
+  PoolSrcPtr src = ((BatchPtr)__builtin_amdgcn_kernarg_segment_ptr())->e[blockIdx.y].src;
+  if (a.S == 1) pool_bwd_body<1, V4>(a, src, blockIdx.x);
+  else pool_bwd_body<2, V4>(a, src, blockIdx.x);
 }
 
 
@@ -840,10 +914,12 @@ void launch_pool_bwd_multi(const PoolBwdBatch& b, hipStream_t st) {
     const PoolBwdArgs& a = b.e[i];
     maxblk = std::max(maxblk, a.N * a.C);
     lds = std::max(lds, sizeof(float) * 2 * a.Ho * a.Wo + a.Ho * a.Wo + 16);
-    v4 = v4 && (a.Ho * a.Wo) % 4 == 0 && (a.H * a.W) % 4 == 0 && a.W % 4 == 0 && al(a.ga.g, 16) && al(a.gm.g, 16) &&
-         al(a.ga.z, 4 * sizeof(zt)) && al(a.gm.z, 4 * sizeof(zt)) && al(a.amax, 4) && al(a.dout_id, 16) &&
-         al(a.gx, 16) && (!a.ga.z || !a.gm.z || a.ga.g == a.gm.g);
-    for (int j = 0; j < a.nextra; ++j) v4 = v4 && al(a.extra[j], 16);
+    v4 = v4 && (a.Ho * a.Wo) % 4 == 0 && (a.H * a.W) % 4 == 0 && a.W % 4 == 0 && al(a.za, 4 * sizeof(zt)) &&
+         al(a.zm, 4 * sizeof(zt)) && al(a.amax, 4) && al(a.gx, 16);
+    for (int e = 0; e < a.nsrc; ++e) {
+      v4 = v4 && al(a.src[e].dout, 16);
+      for (int j = 0; j < a.src[e].nextra; ++j) v4 = v4 && al(a.src[e].extra[j], 16);
+    }
   }
   KSTAMP_ARM(kStampPoolBwd, st)
   if (v4) hipLaunchKernelGGL(pool_bwd_multi_kernel<true>, dim3(maxblk, b.n), dim3(256), lds, st, b);

@@ -34,6 +34,7 @@ import torch
 import torch.nn.functional as F
 
 from ..parallel.comm import Comm
+from ..utils.graphcheck import capture
 from .darts import BNState, DartsLayout, DartsNetwork, accuracy
 
 # validation batches merged per captured eval forward (eval-mode BN normalises every sample with
@@ -472,7 +473,7 @@ class DartsSearch:
         side0 = self._side_folds()
         for fns, colls in groups:
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g), self._scope():
+            with capture(g), self._scope():
                 for fn in fns:
                     fn()
             graphs.append((g, colls))
@@ -563,7 +564,7 @@ class DartsSearch:
                     self._evaluate(sx, sy)
             torch.cuda.current_stream().wait_stream(side)
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with capture(g):
                 out = torch.stack(self._evaluate(sx, sy))
             ent = self._eval_graphs[key] = (g, sx, sy, out)
         g, sx, sy, out = ent

@@ -14,6 +14,15 @@ backward  combine_bwd_reduce (BN-backward sums + d softmax-weights), fold, then 
           dw_bwd_multi / pool_bwd_multi batches; every input gradient is written (not accumulated) by
           its first kernel, so no memsets
 
+Inside a cell (:func:`cell_forward`, :func:`network_loss`) the pooling of a state is done once
+for all the edges that read it with one stride (:func:`pool_groups`): pooling has no parameters
+and its BN no affine part, so the pooled tensors, the argmax and the batch statistics are the
+same for all of them. The forward pools and folds once per group and every edge normalises the
+shared tensors with a BN reference of its own (its running statistics); the backward of a node
+stops at its per-edge conv parts, and once every consumer of a state has run ONE pool_bwd_multi
+entry forms that state's gradient from all its edges (each edge = one source of the entry: its
+dout, BN-backward sums, softmax weights, identity skip and conv parts).
+
 Cross-workgroup sums go to ``REP`` replicas of each accumulator (workgroup b adds
 into replica b % REP) so that no address sees more than grid/REP atomic adds; a
 ``fold_f64`` launch sums the replicas of BN statistics / BN-backward reductions
@@ -344,10 +353,15 @@ class _Edge:
         self.upd = []
 
 
-def _node_forward(xs, ws, specs, bns, params_list, training, momentum, eps, out=None, extra_fold=(), grad=True):
+def _node_forward(xs, ws, specs, bns, params_list, training, momentum, eps, out=None, extra_fold=(), grad=True,
+                  pool_cache=None, pool_keys=None):
     """One node's forward (all kernels of every incoming edge); ``out`` may be a preallocated
     contiguous buffer (the cell writes each node straight into its concat slot). ``grad``: a
-    backward pass may follow (the caller's grad mode). Returns (out, edges) - ``edges`` is the
+    backward pass may follow (the caller's grad mode). ``pool_cache`` (a dict, inside a cell) with
+    ``pool_keys[i]`` = edge i's (source state, stride): the pooled tensors, the argmax and their
+    batch statistics are computed once per key - by the first node that meets it, which also folds
+    the statistics - and every later edge of the key reuses them with a BN reference of its own
+    (its running statistics) over the shared, folded sums. Returns (out, edges) - ``edges`` is the
     state :func:`_node_backward` needs."""
     E = len(specs)
     xs = [t.contiguous() for t in xs]
@@ -389,6 +403,7 @@ def _node_forward(xs, ws, specs, bns, params_list, training, momentum, eps, out=
     pool_groups = defaultdict(list)
     fr_calls = []
     stage1, stage2 = [], []
+    pool_fold = []  # fold segments of the pool statistics this node computed for its cell (pool_cache)
     for e in edges:
         for k, prim in enumerate(e.spec.prims):
             if prim == "none":
@@ -410,6 +425,23 @@ def _node_forward(xs, ws, specs, bns, params_list, training, momentum, eps, out=
                 e.zs[k], e.bns[k] = z, e.refs[sl[0]]
                 e.saved[prim] = (d, z)
                 stage1.append(e.slot0 + sl[0])
+            elif prim in ("avg_pooling_3x3", "max_pooling_3x3") and pool_cache is not None:
+                key = pool_keys[e.i]
+                if key not in pool_cache:  # first edge of this (state, stride): pool once, fold once
+                    za, zm = new(), new()
+                    am = torch.empty(N, C, Ho, Wo, dtype=torch.uint8, device=dev)
+                    pst = zeros64(2 * slot, dev) if training else None
+                    sa, sm = (pst[:slot], pst[slot:]) if training else (None, None)
+                    pool_groups[e.S].append((e.x, za, zm, sa, sm, am))
+                    pool_cache[key] = (za, zm, am, sa, sm)
+                    if training:
+                        pool_fold += [(sa, 2 * C, 2 * C), (sm, 2 * C, 2 * C)]
+                za, zm, am, sa, sm = pool_cache[key]
+                e.saved["pool"] = (za, zm, am)
+                avg = prim == "avg_pooling_3x3"
+                e.zs[k] = za if avg else zm
+                # the shared sums are folded by the node that pooled: rep 1 here and in every later node
+                e.bns[k] = _bn(sa if avg else sm, e.bn[sl[0]][0], e.bn[sl[0]][1], cnt, training, eps, C)
             elif prim in ("avg_pooling_3x3", "max_pooling_3x3"):
                 if "pool" not in e.saved:
                     za, zm = new(), new()
@@ -446,8 +478,8 @@ def _node_forward(xs, ws, specs, bns, params_list, training, momentum, eps, out=
     if fr_calls:
         _launch("pw_fwd", fr_calls, 2)
     defer = training and _defer()
-    if training and stage1 and not defer:
-        _fold([(stats[i * slot:(i + 1) * slot], 2 * C, 2 * C) for i in sorted(set(stage1))])
+    if training and (stage1 or pool_fold) and not defer:
+        _fold([(stats[i * slot:(i + 1) * slot], 2 * C, 2 * C) for i in sorted(set(stage1))] + pool_fold)
     # ---- separable stage 2 (stride 1, input BN-apply prologue)
     s2_groups = defaultdict(list)
     for e in edges:
@@ -463,9 +495,10 @@ def _node_forward(xs, ws, specs, bns, params_list, training, momentum, eps, out=
                 e.zs[k], e.bns[k] = z2, e.refs[sl[1]]
                 e.saved[prim] = (d1, z1, d2, z2)
     _dwpw_multi([(*c, K, 1, 1, K // 2) for K, calls in s2_groups.items() for c in calls])
-    if training and (stage2 or (defer and stage1) or extra_fold):  # (deferred: the stage-1 statistics too)
+    late_pool = pool_fold if defer else []
+    if training and (stage2 or (defer and stage1) or late_pool or extra_fold):  # (deferred: the stage-1 statistics too)
         _fold([(stats[i * slot:(i + 1) * slot], 2 * C, 2 * C)
-               for i in sorted(set(stage2 + (stage1 if defer else [])))] + list(extra_fold))
+               for i in sorted(set(stage2 + (stage1 if defer else [])))] + late_pool + list(extra_fold))
     # ---- weighted sums into the node output
     if out is None:
         out = torch.empty(N, C, Ho, Wo, device=dev)
@@ -481,7 +514,7 @@ def _node_forward(xs, ws, specs, bns, params_list, training, momentum, eps, out=
 
 
 def _node_backward(edges, training, C, dout, gx_of, take_first, sinks, pkey, cell_gw=None, live=None,
-                   alpha_need=True):
+                   alpha_need=True, pool_out=None):
     """One node's backward. ``gx_of(i)`` is the input-gradient buffer of edge i (edges of
     different nodes that read the same state share one buffer); ``take_first(i)`` is True for
     the first kernel that writes it (it overwrites instead of accumulating, so no memset);
@@ -491,7 +524,12 @@ def _node_backward(edges, training, C, dout, gx_of, take_first, sinks, pkey, cel
     runs (:func:`_edge_live`); an edge that is not live gets no input-gradient buffer, no
     temporaries and no BN-backward fold segment, and keeps its combine_bwd_reduce entry only for
     d(alpha) (``alpha_need``). The alpha-weight gradients stay in ``edge.gw`` (f64 replicas, folded
-    unless ``cell_gw`` collects them; None for an edge without an entry)."""
+    unless ``cell_gw`` collects them; None for an edge without an entry).
+    ``pool_out`` (a list, inside a cell): the node runs everything up to the stage-1 / dilated
+    depthwise backward into per-edge part buffers and stops; per live edge it appends (edge, its
+    :func:`_pool_source` or None, its stride-2 skip pw_bwd entry pair or None) and the cell forms
+    each state's gradient later (``take_first`` is not consulted). ``dout`` must then stay
+    unmodified until the cell has launched those entries."""
     dout = dout.contiguous()
     dev = dout.device
     if live is None:
@@ -594,23 +632,6 @@ def _node_backward(edges, training, C, dout, gx_of, take_first, sinks, pkey, cel
 
     # ---- every edge's input gradient: stage-1 separable and dilated depthwise backward, then pools
     # and the identity skip
-    first = {e.i: take_first(e.i) for e in edges}
-
-    def tf(i):  # the first writer of gx_of(i) overwrites it
-        f = first.get(i, False)
-        first[i] = False
-        return f
-
-    def pool_srcs(e):
-        za, zm, am = e.saved["pool"]
-        ga = gm = None
-        for k, p in enumerate(e.spec.prims):
-            if p == "avg_pooling_3x3":
-                ga = src(e, k, za)
-            elif p == "max_pooling_3x3":
-                gm = src(e, k, zm)
-        return ga, gm, am
-
     # every stage-1 separable and dilated depthwise backward of the node in ONE mixed-variant
     # launch, each into its own buffer (no read-modify-write of gx, so no ordering between
     # them); the pool-backward launch then forms gx = pools + identity + those parts, once
@@ -625,29 +646,90 @@ def _node_backward(edges, training, C, dout, gx_of, take_first, sinks, pkey, cel
         dd = e.saved[prim + "/dd1"] if sep else dd_of[(e.i, prim)]
         convs.append((e.x, None, e.P[name], dd, t, g, None, gst, True, K, 1 if sep else 2, e.S))
     _launch("dw_bwd_multi", convs)
+
+    def fr_pair(e):  # stride-2 skip (FactorizedReduce) backward entries of edge e, or None
+        if "skip_connection" not in e.saved:
+            return None
+        k = e.spec.prims.index("skip_connection")
+        (z,) = e.saved["skip_connection"]
+        gs = src(e, k, z)
+        g1, gst1 = sink(e, "skip_connection.conv1")
+        g2, gst2 = sink(e, "skip_connection.conv2")
+        return ((gs, e.P["skip_connection.conv1"], None, e.x, None, gxs[e.i], g1, 0, 0, gst1),
+                (gs, e.P["skip_connection.conv2"], None, e.x, None, gxs[e.i], g2, C // 2, 1, gst2))
+
+    if pool_out is not None:
+        # inside a cell the node stops here: the cell forms each state's gradient in ONE entry from all
+        # the edges that read it, once its last consumer's backward has run (_cell_bwd)
+        for e in edges:
+            pool_out.append((e, _pool_source(e, dout, r_late, C, parts.get(e.i, [])), fr_pair(e)))
+        return
+    first = {e.i: take_first(e.i) for e in edges}
+
+    def tf(i):  # the first writer of gx_of(i) overwrites it
+        f = first.get(i, False)
+        first[i] = False
+        return f
+
     sums = []
     for e in edges:
-        ga, gm, am = pool_srcs(e) if "pool" in e.saved else (None, None, None)
-        ex = parts.get(e.i, [])
-        if ga is None and gm is None and e.id_idx < 0 and not ex:
+        s = _pool_source(e, dout, r_late, C, parts.get(e.i, []))
+        if s is None:
             continue  # only a stride-2 skip (below) or 'none' writes this edge's gradient
-        sums.append((ga, gm, e.x, dout if e.id_idx >= 0 else None, e.w, e.id_idx, gxs[e.i], am, tf(e.i), e.S, ex))
+        sums += _pool_entries([(e, s)], gxs[e.i], tf(e.i))
     _launch("pool_bwd_multi", sums)
     # ---- stride-2 skip (FactorizedReduce): scattered adds, so its gx must exist already
     frc = []
     for e in edges:
-        if "skip_connection" in e.saved:
+        pair = fr_pair(e)
+        if pair is not None:
             if tf(e.i):
                 gxs[e.i].zero_()
-            k = e.spec.prims.index("skip_connection")
-            (z,) = e.saved["skip_connection"]
-            gs = src(e, k, z)
-            g, gst = sink(e, "skip_connection.conv1")
-            frc.append((gs, e.P["skip_connection.conv1"], None, e.x, None, gxs[e.i], g, 0, 0, gst))
-            g, gst = sink(e, "skip_connection.conv2")
-            frc.append((gs, e.P["skip_connection.conv2"], None, e.x, None, gxs[e.i], g, C // 2, 1, gst))
+            frc += pair
     if frc:
         _launch("pw_bwd", frc, 2, 1, True)
+
+
+POOL_SHARE = int(_K.POOL_SHARE)  # edges one pool_bwd_multi entry sums (kMaxShare, csrc/hip/darts_ops.h)
+
+
+def _pool_bn(e, prim):
+    return e.bl[e.widx.index(e.spec.prims.index(prim))]
+
+
+def _pool_source(e, dout, rep, C, extras):
+    """Edge ``e``'s source of a pool_bwd_multi entry - its ``dout``, the per-edge parts of both pools'
+    BN backward (sums read from ``rep`` replicas), its identity weight and its conv input-gradient
+    parts ``extras`` - or None when the edge adds nothing there (only a stride-2 skip or ``none``)."""
+    part = {}
+    if "pool" in e.saved:
+        for k, p in enumerate(e.spec.prims):
+            if p in ("avg_pooling_3x3", "max_pooling_3x3"):
+                j = e.widx.index(k)
+                part[p] = (e.red[:C], e.red[(1 + j) * C:(2 + j) * C], e.w, k, rep, e.nred, e.bl[j][2])
+    if not part and e.id_idx < 0 and not extras:
+        return None
+    return (dout, part.get("avg_pooling_3x3"), part.get("max_pooling_3x3"), e.w if e.id_idx >= 0 else None,
+            e.id_idx, list(extras))
+
+
+def _pool_entries(group, gx, overwrite):
+    """The pool_bwd_multi entries that form ``gx`` from ``group`` = [(edge, its :func:`_pool_source`)],
+    edges that read one state with one stride and share its pooled tensors: POOL_SHARE sources per
+    entry; the first entry overwrites ``gx`` if ``overwrite``, further ones accumulate (so they go
+    into later launches: entries of one launch write distinct buffers)."""
+    out = []
+    for i in range(0, len(group), POOL_SHARE):
+        chunk = group[i:i + POOL_SHARE]
+        za = zm = am = bna = bnm = None
+        for e, s in chunk:
+            if s[1] is not None and za is None:
+                za, bna = e.saved["pool"][0], _pool_bn(e, "avg_pooling_3x3")
+            if s[2] is not None and zm is None:
+                zm, am, bnm = e.saved["pool"][1], e.saved["pool"][2], _pool_bn(e, "max_pooling_3x3")
+        e0 = chunk[0][0]
+        out.append((za, zm, bna, bnm, am, e0.x, gx, overwrite and i == 0, e0.S, [s for _, s in chunk]))
+    return out
 
 
 class _MixedNode(torch.autograd.Function):
@@ -829,6 +911,35 @@ def needed_grads(spec: CellSpec, need0: bool, need1: bool, wreq, alpha: bool) ->
     return need
 
 
+def live_edges(spec: CellSpec, need: Sequence[bool], wreq) -> List[List[bool]]:
+    """Per node and edge of a cell: the edge's operator backward runs in a pass whose
+    :func:`needed_grads` are ``need`` - its node needs a gradient and so does its source state or a
+    parameter of its own (:func:`_edge_live`, on the static :class:`CellSpec`)."""
+    return [[bool(need[2 + i]) and (not NEEDED_GRADS or bool(need[src]) or any(wreq(n) for n in pnames))
+             for _, pnames, _, src, _ in node] for i, node in enumerate(spec.nodes)]
+
+
+def pool_groups(spec: CellSpec, live: Optional[Sequence[Sequence[bool]]] = None) -> Dict[Tuple[int, int], List[Tuple[int, int]]]:
+    """The edges of a cell that read one state with one stride: ``{(source state, stride): [(node,
+    edge), ...]}``, states numbered as in :func:`needed_grads`, members in node order, keys in order
+    of first use. Such edges get identical pooled tensors, argmax and batch statistics (pooling has
+    no parameters and its BN no affine part), so the forward pools once per key (``live`` None: every
+    edge; the per-cell cache of :func:`_node_forward` keys alike) and the backward forms the state's
+    gradient in one pool_bwd_multi entry per key from the edges with ``live[node][edge]``
+    (:func:`live_edges`). Edges whose primitives are all ``none`` contribute nothing and are left
+    out; a key without members does not appear. Pure bookkeeping on the static :class:`CellSpec`, so
+    every rank and both recorded passes of :class:`stacked_passes` group alike."""
+    groups: Dict[Tuple[int, int], List[Tuple[int, int]]] = {}
+    for i, node in enumerate(spec.nodes):
+        for k, (es, _, _, src, _) in enumerate(node):
+            if live is not None and not live[i][k]:
+                continue
+            if all(p == "none" for p in es.prims):
+                continue
+            groups.setdefault((src, es.stride), []).append((i, k))
+    return groups
+
+
 def network_needed_grads(spec: "NetSpec", wreq, alpha_n: bool, alpha_r: bool):
     """:func:`needed_grads` over the whole supernet: (stem output needs a gradient, per cell its
     ``needed_grads`` list). A cell output needs a gradient if any of its nodes does; the stem
@@ -867,6 +978,7 @@ def _cell_fwd(spec, s0, s1, wts, P, bn_of, training, momentum, eps, grad=True):
     Wo = (t0.shape[3] - 1) // max(S) + 1 if S else t0.shape[3]
     O = torch.empty(nn_, N, C, Ho, Wo, device=t0.device)
     node_states = []
+    pool_cache = {}  # (state, stride) -> its pooled tensors, argmax and folded statistics (_node_forward)
     for i, node in enumerate(spec.nodes):
         xs = [states[src] for _, _, _, src, _ in node]
         ws = [wts[row] for _, _, _, _, row in node]
@@ -874,7 +986,8 @@ def _cell_fwd(spec, s0, s1, wts, P, bn_of, training, momentum, eps, grad=True):
         bns = [[bn_of(b) for b in bnames] for _, _, bnames, _, _ in node]
         plist = [[P[n] for n in pnames] for _, pnames, _, _, _ in node]
         out, edges = _node_forward(xs, ws, specs, bns, plist, training, momentum, eps, out=O[i],
-                                   extra_fold=late if i == 0 else (), grad=grad)
+                                   extra_fold=late if i == 0 else (), grad=grad, pool_cache=pool_cache,
+                                   pool_keys=[(src, es.stride) for es, _, _, src, _ in node])
         states.append(out)
         node_states.append(edges)
     return O, (spec, training, st0, st1, node_states, states, wts, P)
@@ -887,11 +1000,15 @@ def _edge_live(e, src_need: bool) -> bool:
 
 
 def _cell_bwd(state, gO, sinks, pkey, gx0, first0, gx1, first1, need0, need1, alpha_rows=None, alpha_need=True):
-    """The cell backward: ``gO`` = gradient of the node outputs (node-major, overwritten by the
-    nodes' input-gradient kernels as scratch), nodes in reverse with one gradient buffer per cell
-    state (the first kernel writing a buffer overwrites it, later ones accumulate), then both
-    preprocess layers into ``gx0`` / ``gx1`` (None: new buffers) - overwriting when ``first0`` /
-    ``first1``. Weight gradients through ``sinks`` under ``pkey(name)``. ``alpha_rows`` (a list):
+    """The cell backward: ``gO`` = gradient of the node outputs (node-major; a node state's slice
+    also receives the gradients of the edges that read it), nodes in reverse with one gradient
+    buffer per cell state, then both preprocess layers into ``gx0`` / ``gx1`` (None: new buffers) -
+    overwriting when ``first0`` / ``first1``. A node's backward stops at its per-edge conv parts;
+    after the backward of a state's earliest consumer - node i for node i - 1, node 0 for both
+    preprocessed inputs - one pool_bwd_multi entry per (state, stride) group (:func:`pool_groups`
+    over the live edges) forms the state's gradient from all its edges, overwriting a buffer nobody
+    wrote yet and adding to a node state's concat gradient; the stride-2 skips' scattered adds
+    follow it. So each consumer's ``dout`` is complete and stays unmodified until it is read. Weight gradients through ``sinks`` under ``pkey(name)``. ``alpha_rows`` (a list):
     the edges' replicated d(softmax weight) go there as (f64 replicas, rstride, weight row) for the
     alpha-gradient kernel; otherwise they are folded and returned as a [rows, K] tensor.
     ``alpha_need``: this cell type's softmax weights need a gradient. Only what the pass needs runs
@@ -908,26 +1025,60 @@ def _cell_bwd(state, gO, sinks, pkey, gx0, first0, gx1, first1, need0, need1, al
     first = [True, True] + [False] * nn_
     ga_rows = [None] * nn_
     cell_gw = []  # the nodes' unfolded d(alpha) replicas
+    lives = live_edges(spec, need, lambda n: P[n].requires_grad)
+    groups = pool_groups(spec, lives)
+    # a state's gradient is formed once, after the backward of its earliest (= last to run) consumer
+    ready = defaultdict(list)
+    for key, members in groups.items():
+        ready[min(i for i, _ in members)].append(key)
+    recs = {}  # (node, edge) -> (edge state, pool source, stride-2 skip entries), from _node_backward
+
+    def form_states(keys):
+        """The gradient buffers of the states in ``keys`` (= (state, stride) groups whose consumers
+        have all run): one pool_bwd_multi entry per group summing its edges' pools, identity skips and
+        conv parts, then the stride-2 skips' scattered adds."""
+        rounds, frs = defaultdict(list), defaultdict(list)
+        depth = defaultdict(int)  # entries of one launch write distinct buffers
+        for key in keys:
+            src = key[0]
+            got = [recs.pop(m) for m in groups[key]]
+            srcs_ = [(e, s) for e, s, _ in got if s is not None]
+            if srcs_:
+                for ent in _pool_entries(srcs_, gS[src], first[src]):
+                    rounds[depth[src]].append(ent)
+                    depth[src] += 1
+                first[src] = False
+            frs[src] += [fr for _, _, fr in got if fr is not None]
+        for r in sorted(rounds):
+            _launch("pool_bwd_multi", rounds[r])
+        # stride-2 skips add into gx without atomics: the edges of one state go out one launch after the
+        # other, the r-th edge of every state together
+        for src, pairs in frs.items():
+            if pairs and first[src]:
+                gS[src].zero_()
+                first[src] = False
+        for r in range(max((len(v) for v in frs.values()), default=0)):
+            _launch("pw_bwd", [c for pairs in frs.values() if r < len(pairs) for c in pairs[r]], 2, 1, True)
+
     for i in reversed(range(nn_)):
-        if not need[2 + i]:
+        if not need[2 + i]:  # (it has no live edge, so no group becomes ready here)
             continue
         node = spec.nodes[i]
         edges = node_states[i]
         srcs = [src for _, _, _, src, _ in node]
-        live = [_edge_live(e, need[src]) for e, src in zip(edges, srcs)]
+        live = lives[i]
         for src, lv in zip(srcs, live):
             # (a live edge from a state that needs no gradient - a parameter of its own does - still
             # writes its input gradient: into a buffer nobody reads)
             if lv and gS[src] is None:
                 gS[src] = torch.empty_like(states[src])
 
-        def take_first(k, srcs=srcs):
-            f = first[srcs[k]]
-            first[srcs[k]] = False
-            return f
-
-        _node_backward(edges, training, spec.C, gS[2 + i], lambda k, srcs=srcs: gS[srcs[k]], take_first, sinks,
-                       lambda e, name, node=node: pkey(node[e.i][1][e.spec.pidx[name]]), cell_gw, live, alpha_need)
+        out = []  # (first writers are settled by form_states: no take_first)
+        _node_backward(edges, training, spec.C, gS[2 + i], lambda k, srcs=srcs: gS[srcs[k]], None, sinks,
+                       lambda e, name, node=node: pkey(node[e.i][1][e.spec.pidx[name]]), cell_gw, live, alpha_need, out)
+        for e, s, fr in out:
+            recs[(i, e.i)] = (e, s, fr)
+        form_states(ready.get(i, []))
         if alpha_rows is not None:
             for e, (_, _, _, _, row) in zip(edges, node):
                 if e.gw is not None:

@@ -16,6 +16,8 @@ from typing import Optional
 import torch
 import torch.distributed as dist
 
+from ..utils.graphcheck import capture
+
 
 class Comm:
     def __init__(self, rank: int = 0, world_size: int = 1, local_rank: int = 0, backend: Optional[str] = None,
@@ -157,7 +159,7 @@ class Comm:
             dist.all_reduce(x, group=self.group)  # communicator set up outside the capture
             torch.cuda.synchronize(self.device)
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with capture(g):
                 dist.all_reduce(x, group=self.group)
         except Exception:  # noqa: BLE001 - any failure keeps the collectives on the host
             ok, g = False, None

@@ -9,11 +9,22 @@ once in a while when stale data happens to be bad. This is how the round-2 ENAS 
 root-caused (scripts/enas_nan_locate.py): PyTorch's cross-workgroup reductions (``mean`` /
 ``sum`` over the non-innermost dims of channels-last bf16 tensors) read their staging buffer
 before writing it when replayed from a graph on this ROCm stack.
+
+:func:`capture` is how this package captures: no object is destroyed by Python's cyclic garbage
+collector while a capture is under way. ``torch.cuda.graph`` no longer collects before it
+captures, and trainers here sit in reference cycles with their captured steps (the step closes
+over its trainer), so a ``CUDAGraph`` that nobody uses any more lives until a collection - and
+one that starts inside a LATER capture destroys it there. Destroying a captured graph
+synchronises the device on ROCm, which a capturing thread may not do: the error is raised in a
+destructor and ends the process (an abort in the middle of an unrelated test's capture, with the
+interpreter reporting "Garbage-collecting").
 """
 
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import gc
 
 import torch
 
@@ -43,3 +54,19 @@ def poison_graph_pool(graph: "torch.cuda.CUDAGraph") -> int:
         n += seg["total_size"]
     torch.cuda.synchronize()
     return n
+
+
+@contextlib.contextmanager
+def capture(graph: "torch.cuda.CUDAGraph", **kwargs):
+    """``with capture(g): ...`` - the ``torch.cuda.graph`` context (same ``kwargs``) with the garbage of earlier work
+    collected BEFORE the capture begins and the cyclic collector off until it has ended (see the
+    module docstring); the collector's state is restored on the way out, also after an error."""
+    gc.collect()
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, **kwargs):
+            yield graph
+    finally:
+        if was_on:
+            gc.enable()

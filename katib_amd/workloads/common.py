@@ -19,6 +19,8 @@ from typing import Callable, Dict, Optional, Tuple
 
 import torch
 
+from ..utils.graphcheck import capture
+
 
 def device() -> torch.device:
     if torch.cuda.is_available():
@@ -196,7 +198,7 @@ class CapturedStep:
                 self.calls += 1
                 return out
             self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
+            with capture(self.graph):
                 self.out = self.fn()
         self.graph.replay()
         return self.out
