@@ -305,13 +305,17 @@ __global__ __launch_bounds__(256) void gelu_bwd_k(const u16* __restrict__ u, con
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
 
+// The cross-entropy kernels keep the running maximum m in the logits' own units and sum
+// exp2((x - m) * log2(e)): x - m is exactly 0 at the maximum (and rounds once, to fp32, elsewhere), so a
+// row's largest term is exactly 1, lse = m + ln(s) carries no rounding of m, and loss = (m - x_target) + ln(s)
+// is exactly 0 when the target holds all the mass (one column, or one logit far above the rest).
 __device__ __forceinline__ void block_max_sum(float& m, float& s, float* sh) {
-  // combine (max, sum-of-exp2) pairs across the 4 waves of a 256-thread block
+  // combine (max, sum-of-exp) pairs across the 4 waves of a 256-thread block
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
     const float mn = fmaxf(m, m2);
-    s = (mn == -INFINITY) ? 0.f : s * exp2f(m - mn) + s2 * exp2f(m2 - mn);
+    s = (mn == -INFINITY) ? 0.f : s * exp2f((m - mn) * kLog2e) + s2 * exp2f((m2 - mn) * kLog2e);
     m = mn;
   }
   const int w = threadIdx.x >> 6;
@@ -325,7 +329,7 @@ __device__ __forceinline__ void block_max_sum(float& m, float& s, float* sh) {
   for (int i = 1; i < 4; ++i) mm = fmaxf(mm, sh[2 * i]);
   float ss = 0.f;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) ss += sh[2 * i + 1] * exp2f(sh[2 * i] - mm);
+  for (int i = 0; i < 4; ++i) ss += sh[2 * i + 1] * exp2f((sh[2 * i] - mm) * kLog2e);
   m = mm;
   s = ss;
 }
@@ -342,8 +346,8 @@ __global__ __launch_bounds__(256) void xent_fwd_k(const u16* __restrict__ logits
     float x[8];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      x[2 * k] = lo2f(q[k]) * kLog2e;
-      x[2 * k + 1] = hi2f(q[k]) * kLog2e;
+      x[2 * k] = lo2f(q[k]);
+      x[2 * k + 1] = hi2f(q[k]);
     }
     if (8 * c + 8 > V) {
 #pragma unroll
@@ -357,17 +361,17 @@ __global__ __launch_bounds__(256) void xent_fwd_k(const u16* __restrict__ logits
     if (mn == -INFINITY) continue;
     float cs = 0.f;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) cs += exp2f(x[e] - mn);
-    s = s * exp2f(m - mn) + cs;
+    for (int e = 0; e < 8; ++e) cs += exp2f((x[e] - mn) * kLog2e);
+    s = s * exp2f((m - mn) * kLog2e) + cs;
     m = mn;
   }
   block_max_sum(m, s, sh);
   if (threadIdx.x == 0) {
-    const float l = (m + log2f(s)) * kLn2;
+    const float ls = log2f(s) * kLn2;
     const int64_t t = tgt[row];
     const float xt = (t >= 0 && t < V) ? bf2f(L[t]) : 0.f;
-    lse[row] = l;
-    loss[row] = l - xt;
+    lse[row] = m + ls;
+    loss[row] = (m - xt) + ls;  // xt = 0 for an out-of-range target: the row's lse
   }
 }
 
@@ -386,7 +390,7 @@ __global__ __launch_bounds__(256) void xent_eval_k(const u16* __restrict__ logit
   int bi = 0x7fffffff;
   for (int c = threadIdx.x; c < nch; c += 256) {
     const u32x4 q = reinterpret_cast<const u32x4*>(L)[c];
-    float r[8], x[8];
+    float r[8];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       r[2 * k] = lo2f(q[k]);
@@ -395,21 +399,23 @@ __global__ __launch_bounds__(256) void xent_eval_k(const u16* __restrict__ logit
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       if (8 * c + e >= V) r[e] = -INFINITY;
-      x[e] = r[e] * kLog2e;
       if (r[e] > bv) {  // strictly greater: the first index of a tie stays (columns ascend per thread)
         bv = r[e];
         bi = 8 * c + e;
       }
     }
-    float cm = x[0];
+    float cm = r[0];
 #pragma unroll
-    for (int e = 1; e < 8; ++e) cm = fmaxf(cm, x[e]);
+    for (int e = 1; e < 8; ++e) cm = fmaxf(cm, r[e]);
     const float mn = fmaxf(m, cm);
     if (mn == -INFINITY) continue;
     float cs = 0.f;
+    // v_exp_f32 directly (as xent_fused_k): the arguments are <= 0 and the row's sum is >= 1, so the
+    // terms below 2^-126 that exp2f's range handling would keep cannot reach it; this kernel is
+    // VALU-bound (the argmax shares the loop) and that handling is 4 instructions per logit
 #pragma unroll
-    for (int e = 0; e < 8; ++e) cs += exp2f(x[e] - mn);
-    s = s * exp2f(m - mn) + cs;
+    for (int e = 0; e < 8; ++e) cs += __builtin_amdgcn_exp2f((r[e] - mn) * kLog2e);
+    s = s * exp2f((m - mn) * kLog2e) + cs;
     m = mn;
   }
   block_max_sum(m, s, sh);
@@ -436,10 +442,9 @@ __global__ __launch_bounds__(256) void xent_eval_k(const u16* __restrict__ logit
         bv = shv[w];
         bi = shi[w];
       }
-    const float l = (m + log2f(s)) * kLn2;
     const int64_t t = tgt[row];
     const float xt = (t >= 0 && t < V) ? bf2f(L[t]) : 0.f;
-    loss[row] = l - xt;
+    loss[row] = (m - xt) + log2f(s) * kLn2;
     hit[row] = (t == (int64_t)bi) ? 1.f : 0.f;
   }
 }
@@ -450,7 +455,7 @@ __global__ __launch_bounds__(256) void xent_bwd_k(u16* __restrict__ logits, cons
   const int row = blockIdx.x;
   u16* L = logits + (int64_t)row * Vp;
   const int nch = Vp >> 3;
-  const float l2 = lse[row] * kLog2e;
+  const float l = lse[row];
   const float sc = gscale[0] * inv_n;
   const int64_t t = tgt[row];
   for (int c = threadIdx.x; c < nch; c += 256) {
@@ -458,8 +463,8 @@ __global__ __launch_bounds__(256) void xent_bwd_k(u16* __restrict__ logits, cons
     float g[8];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      g[2 * k] = exp2f(lo2f(q[k]) * kLog2e - l2);
-      g[2 * k + 1] = exp2f(hi2f(q[k]) * kLog2e - l2);
+      g[2 * k] = exp2f((lo2f(q[k]) - l) * kLog2e);
+      g[2 * k + 1] = exp2f((hi2f(q[k]) - l) * kLog2e);
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -513,7 +518,6 @@ __global__ __launch_bounds__(512, 4) void xent_fused_k(u16* __restrict__ logits,
   m = sh[0];
 #pragma unroll
   for (int i = 1; i < kW; ++i) m = fmaxf(m, sh[i]);
-  m *= kLog2e;
   float s = 0.f;
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
@@ -522,8 +526,8 @@ __global__ __launch_bounds__(512, 4) void xent_fused_k(u16* __restrict__ logits,
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int col = 8 * c + 2 * k;
-      if (col < V) s += __builtin_amdgcn_exp2f(lo2f(q[j][k]) * kLog2e - m);
-      if (col + 1 < V) s += __builtin_amdgcn_exp2f(hi2f(q[j][k]) * kLog2e - m);
+      if (col < V) s += __builtin_amdgcn_exp2f((lo2f(q[j][k]) - m) * kLog2e);
+      if (col + 1 < V) s += __builtin_amdgcn_exp2f((hi2f(q[j][k]) - m) * kLog2e);
     }
   }
 #pragma unroll
@@ -533,10 +537,10 @@ __global__ __launch_bounds__(512, 4) void xent_fused_k(u16* __restrict__ logits,
   s = 0.f;
 #pragma unroll
   for (int i = 0; i < kW; ++i) s += sh[kW + i];
-  const float l2 = m + log2f(s);  // log2-domain lse
+  const float ls2 = log2f(s);  // log2 of the sum of exp(x - m)
   if (threadIdx.x == 0) {
-    lse[row] = l2 * kLn2;
-    loss[row] = l2 * kLn2 - xt;  // xt = 0 for an out-of-range target, as in xent_fwd_k
+    lse[row] = m + ls2 * kLn2;
+    loss[row] = (m - xt) + ls2 * kLn2;  // xt = 0 for an out-of-range target, as in xent_fwd_k
   }
   const float sc = gscale[0] * inv_n;
 #pragma unroll
@@ -546,8 +550,8 @@ __global__ __launch_bounds__(512, 4) void xent_fused_k(u16* __restrict__ logits,
     float g[8];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      g[2 * k] = __builtin_amdgcn_exp2f(lo2f(q[j][k]) * kLog2e - l2);
-      g[2 * k + 1] = __builtin_amdgcn_exp2f(hi2f(q[j][k]) * kLog2e - l2);
+      g[2 * k] = __builtin_amdgcn_exp2f((lo2f(q[j][k]) - m) * kLog2e - ls2);
+      g[2 * k + 1] = __builtin_amdgcn_exp2f((hi2f(q[j][k]) - m) * kLog2e - ls2);
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) {

@@ -9,6 +9,8 @@ import math
 import pytest
 import torch
 
+import gpt2_kernel_oracle as O
+
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda", 0)
@@ -174,8 +176,13 @@ def test_flat_gpt_step_both_dropouts_hip_vs_torch(ops):
         assert _rel(mh.g[n], mr.g[n]) < 6e-2, (n, _rel(mh.g[n], mr.g[n]))
     assert _rel(mh.g["blocks.1.qkv.weight"], m0.g["blocks.1.qkv.weight"]) > 6e-2  # attention dropout did act
     assert float(l0) != float(lh)
+    # the update itself, row by row, against AdamW in fp64 on the gradient each model computed (see
+    # tests/test_gpu_transformer.py::test_flat_gpt_step_hip_vs_torch)
+    uh, ur = O.StepUpdate(mh), O.StepUpdate(mr)
     mh.optimizer_step()
     mr.optimizer_step()
+    uh.check("flat step update hip")
+    ur.check("flat step update torch")
     assert _rel(mh.p32, mr.p32) < 1e-3
 
 

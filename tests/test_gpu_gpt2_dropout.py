@@ -7,10 +7,14 @@ import math
 import pytest
 import torch
 
+import gpt2_kernel_oracle as O
+
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda", 0)
-M = 333  # not a multiple of the forward's 4 rows per workgroup nor of the backward's row stride
+# not a multiple of the forward's 4 rows per workgroup; below the backward's row stride of 336, so a wave's
+# second row and second iteration never run here (tests/test_gpu_gpt2_kernels.py has M = 1029 and 2051)
+M = 333
 SHAPES = [256, 768, 1024, 2048]
 SEED = (3 << 32) | 77  # both key words in use
 
@@ -175,8 +179,13 @@ def test_flat_gpt_step_dropout_hip_vs_torch(ops):
         assert _rel(mh.g[n], mr.g[n]) < 6e-2, (n, _rel(mh.g[n], mr.g[n]))
     assert _rel(mh.g["blocks.1.fc2.weight"], m0.g["blocks.1.fc2.weight"]) > 6e-2  # dropout did act
     assert float(l0) != float(lh)
+    # the update itself, row by row, against AdamW in fp64 on the gradient each model computed (see
+    # tests/test_gpu_transformer.py::test_flat_gpt_step_hip_vs_torch)
+    uh, ur = O.StepUpdate(mh), O.StepUpdate(mr)
     mh.optimizer_step()
     mr.optimizer_step()
+    uh.check("flat step update hip")
+    ur.check("flat step update torch")
     assert _rel(mh.p32, mr.p32) < 1e-3
 
 
