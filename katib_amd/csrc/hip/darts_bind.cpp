@@ -662,6 +662,7 @@ void register_darts_optim(py::module& m);  // darts_optim_bind.cpp
 void register_darts_head(py::module& m);  // darts_head_bind.cpp
 void register_resnet(py::module& m);  // resnet_bind.cpp
 void register_augment(py::module& m);  // augment_bind.cpp
+void register_mnist_cnn(py::module& m);  // mnist_cnn_bind.cpp
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "katib_amd HIP kernels for gfx950 (DARTS edge ops, implicit-GEMM conv, transformer, xGMI all-reduce)";
@@ -700,4 +701,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_darts_head(m);
   register_resnet(m);
   register_augment(m);
+  register_mnist_cnn(m);
 }
