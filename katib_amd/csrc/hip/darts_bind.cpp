@@ -663,6 +663,7 @@ void register_darts_head(py::module& m);  // darts_head_bind.cpp
 void register_resnet(py::module& m);  // resnet_bind.cpp
 void register_augment(py::module& m);  // augment_bind.cpp
 void register_mnist_cnn(py::module& m);  // mnist_cnn_bind.cpp
+void register_mnist_tfcnn(py::module& m);  // mnist_tfcnn_bind.cpp
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "katib_amd HIP kernels for gfx950 (DARTS edge ops, implicit-GEMM conv, transformer, xGMI all-reduce)";
@@ -702,4 +703,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   register_resnet(m);
   register_augment(m);
   register_mnist_cnn(m);
+  register_mnist_tfcnn(m);
 }

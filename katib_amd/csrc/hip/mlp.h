@@ -12,6 +12,14 @@ typedef __hip_bfloat16 bf16;
 // y[M][N] = epi(x[idx?][K] . w[N][K]^T); epi = + bias (may be null), ReLU if relu, * [mask > 0] if mask.
 hipError_t lin_fwd(const bf16* x, const int64_t* idx, const bf16* w, const float* bias, const bf16* mask, bf16* y,
                    int M, int N, int K, int relu, hipStream_t st);
+// The same product for K much larger than M, without gather and mask: slabs of SPLITK_KS columns of K, one
+// per workgroup and 64 x 64 tile, into fp32 partials part [splitk_slabs(K)][M][N]; a second launch sums them
+// in slab order, then bias, ReLU and the bf16 rounding. SPLITK_KS does not depend on M, so a row's result
+// does not depend on the batch it sits in. N % 8 == 0, K % 8 == 0.
+constexpr int SPLITK_KS = 512;
+inline int splitk_slabs(int K) { return (K + SPLITK_KS - 1) / SPLITK_KS; }
+hipError_t lin_fwd_splitk(const bf16* x, const bf16* w, const float* bias, float* part, bf16* y, int M, int N, int K,
+                          int relu, hipStream_t st);
 // dW = dy^T x (x rows through idx when given) and SGD with momentum on w (fp32 [N][K]), its momentum
 // buffer, bf16 shadows w16 [N][K] / w16t [K][N]; bias (+ its buffer) updated from the column sums of dy.
 hipError_t lin_wgrad_sgd(const bf16* dy, const bf16* x, const int64_t* idx, int M, int N, int K, float* w, float* wm,

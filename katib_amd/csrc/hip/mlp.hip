@@ -8,7 +8,11 @@
 //             minibatch indices into the device-resident dataset), bias + ReLU epilogue, or
 //             a ReLU-derivative mask epilogue (dgrad: dX = (dY W) * [X_act > 0] with the
 //             transposed bf16 weight shadow as the K-contiguous operand).
-//  lin_wgrad  dW = dY^T X reduced over the whole minibatch inside one workgroup (the
+//  lin_fwd_splitk  the same product for K much larger than M (the Keras MNIST CNN's fc1: M <= 64, N = 128,
+//             K = 21,632, two output tiles): the same main loop over slabs of SPLITK_KS columns, one workgroup
+//             per slab and tile, into fp32 partials; a second launch sums a row's slabs in slab order, then
+//             bias, ReLU and the bf16 rounding. No gather, no mask.
+//  lin_wgrad dW = dY^T X reduced over the whole minibatch inside one workgroup (the
 //             minibatch is the reduction, <= a few hundred rows), both operands read with
 //             ds_read_b64_tr_b16, and the optimizer applied in the epilogue to the fp32
 //             master and its state, with the bf16 weight and transposed-weight shadows
@@ -28,6 +32,7 @@
 #include <type_traits>
 
 #include "mlp.h"
+#include "mlp_optim.h"
 
 namespace katib_hip {
 namespace mlp {
@@ -46,17 +51,15 @@ __device__ __forceinline__ float bf2f(u16 b) { return __uint_as_float((uint32_t)
 __device__ __forceinline__ u16 f2bf(float f) { return __builtin_bit_cast(u16, (__bf16)f); }
 
 // ------------------------------------------------------------------ Y = epi(A B^T)
-// A [M][K] (rows optionally gathered through idx), B [N][K], both K-contiguous; K % 8 == 0.
-// epi: + bias, ReLU (relu != 0), or * [mask > 0] (mask [M][N] bf16). Output bf16 [M][N].
-__global__ __launch_bounds__(256) void gemm_nt_k(const u16* __restrict__ A, const int64_t* __restrict__ idx,
-                                                 const u16* __restrict__ B, const float* __restrict__ bias,
-                                                 const u16* __restrict__ mask, u16* __restrict__ Y, int M, int N,
-                                                 int K, int relu) {
-  __shared__ __align__(16) u16 smem[2 * (BM + BN) * LD];
+// The MFMA main loop of one 64 x 64 output tile at (m0, n0) over k in [kb, ke): A [M][K] (rows optionally
+// gathered through idx), B [N][K], both K-contiguous; K % 8 == 0, kb % 8 == 0, ke % 8 == 0. smem holds
+// 2 * (BM + BN) * LD elements. acc[a][b][j]: row m0 + wr * 32 + a * 16 + 4 * (lane >> 4) + j, column
+// n0 + wc * 32 + b * 16 + (lane & 15); rows >= M and columns >= N accumulate zeros.
+__device__ __forceinline__ void gemm_nt_tile(const u16* __restrict__ A, const int64_t* __restrict__ idx,
+                                             const u16* __restrict__ B, int M, int N, int K, int m0, int n0, int kb,
+                                             int ke, u16* smem, f32x4 (&acc)[2][2]) {
   u16* As = smem;
   u16* Bs = smem + 2 * BM * LD;
-  const int tilesN = (N + BN - 1) / BN;
-  const int m0 = (blockIdx.x / tilesN) * BM, n0 = (blockIdx.x % tilesN) * BN;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, wr = wid >> 1, wc = wid & 1;
   const int kc = tid & 7, trow = tid >> 3;  // 32 rows x 8 chunks of 16 B per pass
   const u16* arow[2];
@@ -74,8 +77,8 @@ __global__ __launch_bounds__(256) void gemm_nt_k(const u16* __restrict__ A, cons
   u32x4 ra[2], rb[2];
   const u32x4 zero = {0u, 0u, 0u, 0u};
   auto gload = [&](int kt) {
-    const int kk = kt * BK + kc * 8;
-    const bool kin = kk < K;
+    const int kk = kb + kt * BK + kc * 8;
+    const bool kin = kk < ke;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       ra[i] = (kin && aok[i]) ? *reinterpret_cast<const u32x4*>(arow[i] + kk) : zero;
@@ -89,12 +92,11 @@ __global__ __launch_bounds__(256) void gemm_nt_k(const u16* __restrict__ A, cons
       *reinterpret_cast<u32x4*>(Bs + (buf * BN + trow + 32 * i) * LD + kc * 8) = rb[i];
     }
   };
-  f32x4 acc[2][2];
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
     for (int b = 0; b < 2; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const int nk = (K + BK - 1) / BK;
+  const int nk = (ke - kb + BK - 1) / BK;
   gload(0);
   sstore(0);
   __syncthreads();
@@ -121,6 +123,19 @@ __global__ __launch_bounds__(256) void gemm_nt_k(const u16* __restrict__ A, cons
     if (kt + 1 < nk) sstore(buf ^ 1);
     __syncthreads();
   }
+}
+
+// epi: + bias, ReLU (relu != 0), or * [mask > 0] (mask [M][N] bf16). Output bf16 [M][N].
+__global__ __launch_bounds__(256) void gemm_nt_k(const u16* __restrict__ A, const int64_t* __restrict__ idx,
+                                                 const u16* __restrict__ B, const float* __restrict__ bias,
+                                                 const u16* __restrict__ mask, u16* __restrict__ Y, int M, int N,
+                                                 int K, int relu) {
+  __shared__ __align__(16) u16 smem[2 * (BM + BN) * LD];
+  const int tilesN = (N + BN - 1) / BN;
+  const int m0 = (blockIdx.x / tilesN) * BM, n0 = (blockIdx.x % tilesN) * BN;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, wr = wid >> 1, wc = wid & 1, fr = lane & 15;
+  f32x4 acc[2][2];
+  gemm_nt_tile(A, idx, B, M, N, K, m0, n0, 0, K, smem, acc);
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -140,35 +155,55 @@ __global__ __launch_bounds__(256) void gemm_nt_k(const u16* __restrict__ A, cons
     }
 }
 
+// ------------------------------------------------------------------ split-K: Y = act(A B^T + bias), K >> M
+// Slab s of KS columns of one 64 x 64 tile per workgroup (the main loop above over [s KS, (s + 1) KS)), fp32
+// partials P [slabs][M][N]; then splitk_reduce_k sums a row's slabs in slab order, adds the bias, applies ReLU
+// and rounds. KS is a constant, so a row's result does not depend on M: not on the batch it sits in.
+__global__ __launch_bounds__(256) void gemm_nt_slab_k(const u16* __restrict__ A, const u16* __restrict__ B,
+                                                      float* __restrict__ P, int M, int N, int K) {
+  __shared__ __align__(16) u16 smem[2 * (BM + BN) * LD];
+  const int tilesN = (N + BN - 1) / BN, tilesM = (M + BM - 1) / BM;
+  const int slab = blockIdx.x / (tilesM * tilesN), tile = blockIdx.x % (tilesM * tilesN);
+  const int m0 = (tile / tilesN) * BM, n0 = (tile % tilesN) * BN;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, wr = wid >> 1, wc = wid & 1, fr = lane & 15;
+  f32x4 acc[2][2];
+  gemm_nt_tile(A, nullptr, B, M, N, K, m0, n0, slab * SPLITK_KS, min((slab + 1) * SPLITK_KS, K), smem, acc);
+  float* __restrict__ Ps = P + (int64_t)slab * M * N;
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const int col = n0 + wc * 32 + b * 16 + fr;
+      if (col >= N) continue;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int row = m0 + wr * 32 + a * 16 + 4 * (lane >> 4) + j;
+        if (row < M) Ps[(int64_t)row * N + col] = acc[a][b][j];
+      }
+    }
+}
+
+// one thread per 4 consecutive outputs (N % 4 == 0), 16 bytes per slab, summed in slab order
+__global__ __launch_bounds__(256) void splitk_reduce_k(const float* __restrict__ P, int slabs,
+                                                       const float* __restrict__ bias, u16* __restrict__ Y, int MN,
+                                                       int N, int relu) {
+  const int o = (blockIdx.x * 256 + threadIdx.x) * 4;
+  if (o >= MN) return;
+  f32x4 s = *reinterpret_cast<const f32x4*>(P + o);
+#pragma unroll 8
+  for (int k = 1; k < slabs; ++k) s += *reinterpret_cast<const f32x4*>(P + (int64_t)k * MN + o);
+  if (bias) s += *reinterpret_cast<const f32x4*>(bias + o % N);
+  u16 h[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) h[j] = f2bf(relu ? fmaxf(s[j], 0.f) : s[j]);
+  *reinterpret_cast<uint2*>(Y + o) = uint2{(uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16)};
+}
+
 // Element updates of the two-state optimizers: operator() takes the gradient, the element's two
 // state values (updated in place) and its weight, and returns the new weight. Both leave an
 // element with g = 0 and zero state exactly as it was (the padded output rows, dead ReLU units).
-//
-// torch.optim.Adam, default flags: s0 = exp_avg, s1 = exp_avg_sq. step = lr / (1 - beta1^t) and
-// sbc2 = sqrt(1 - beta2^t) are the same for every element; init() computes them once per thread.
-struct AdamUpd {
-  float b1, b2, eps;
-  const int* step_t;
-  float step, sbc2;
-  // beta^t by binary exponentiation: exact at t = 1, where 1 - beta2^t = 1e-3 magnifies an error of
-  // beta2^t a thousandfold, and within t * 2^-24 relative anywhere
-  static __device__ __forceinline__ float ipow(float b, int t) {
-    float r = 1.f;
-    for (; t > 0; t >>= 1, b *= b)
-      if (t & 1) r *= b;
-    return r;
-  }
-  __device__ __forceinline__ void init(float lr) {
-    const int t = max(step_t[0], 1);  // 1-based; a counter nobody advanced must not divide by 0
-    step = lr / (1.f - ipow(b1, t));
-    sbc2 = sqrtf(1.f - ipow(b2, t));
-  }
-  __device__ __forceinline__ float operator()(float g, float& m, float& v, float w) const {
-    m = b1 * m + (1.f - b1) * g;
-    v = b2 * v + (1.f - b2) * (g * g);
-    return w - step * (m / (sqrtf(v) / sbc2 + eps));  // zero state, g = 0: 0 / eps = 0
-  }
-};
+// AdamUpd (torch.optim.Adam, default flags: s0 = exp_avg, s1 = exp_avg_sq) is in mlp_optim.h, which
+// mnist_tfcnn.hip shares.
 // The trial's Ftrl class (FTRL-proximal as MXNet's), operation for operation: s0 = z, s1 = n.
 struct FtrlUpd {
   float l1, beta, wd;
@@ -440,6 +475,19 @@ hipError_t lin_fwd(const bf16* x, const int64_t* idx, const bf16* w, const float
   hipLaunchKernelGGL(gemm_nt_k, dim3(grid), dim3(256), 0, st, reinterpret_cast<const u16*>(x), idx,
                      reinterpret_cast<const u16*>(w), bias, reinterpret_cast<const u16*>(mask),
                      reinterpret_cast<u16*>(y), M, N, K, relu);
+  return hipGetLastError();
+}
+
+hipError_t lin_fwd_splitk(const bf16* x, const bf16* w, const float* bias, float* part, bf16* y, int M, int N, int K,
+                          int relu, hipStream_t st) {
+  const int slabs = splitk_slabs(K);
+  const int grid = ((M + BM - 1) / BM) * ((N + BN - 1) / BN) * slabs;
+  hipLaunchKernelGGL(gemm_nt_slab_k, dim3(grid), dim3(256), 0, st, reinterpret_cast<const u16*>(x),
+                     reinterpret_cast<const u16*>(w), part, M, N, K);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(splitk_reduce_k, dim3((M * N / 4 + 255) / 256), dim3(256), 0, st, part, slabs, bias,
+                     reinterpret_cast<u16*>(y), M * N, N, relu);
   return hipGetLastError();
 }
 

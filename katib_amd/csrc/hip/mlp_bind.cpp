@@ -45,6 +45,25 @@ void lin_fwd(const Tensor& x, const c10::optional<Tensor>& idx, const Tensor& w,
      "lin_fwd");
 }
 
+int64_t splitk_part_size(int64_t M, int64_t N, int64_t K) { return (int64_t)M_::splitk_slabs((int)K) * M * N; }
+
+void lin_fwd_splitk(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& bias, const Tensor& part,
+                    const Tensor& y, bool relu) {
+  TORCH_CHECK(w.dim() == 2 && y.dim() == 2 && x.dim() == 2, "lin_fwd_splitk: 2-D operands");
+  const int64_t N = w.size(0), K = w.size(1), M = y.size(0);
+  TORCH_CHECK(M > 0 && K > 0 && K % 8 == 0 && N % 8 == 0 && K == x.size(1) && y.size(1) == N && x.size(0) == M,
+              "lin_fwd_splitk: N, K % 8 == 0 and matching shapes");
+  TORCH_CHECK(M * N < (1 << 28) && K < (1 << 28), "lin_fwd_splitk: operands too large");
+  chk(x, at::kBFloat16, M * K, "x");
+  chk(w, at::kBFloat16, N * K, "w");
+  chk(y, at::kBFloat16, M * N, "y");
+  chk(part, at::kFloat, splitk_part_size(M, N, K), "part");
+  if (bias.has_value()) chk(*bias, at::kFloat, N, "bias");
+  ok(M_::lin_fwd_splitk(bp(x), bp(w), bias.has_value() ? bias->data_ptr<float>() : nullptr, part.data_ptr<float>(),
+                        bp(y), (int)M, (int)N, (int)K, relu ? 1 : 0, stream()),
+     "lin_fwd_splitk");
+}
+
 void lin_wgrad_sgd(const Tensor& dy, const Tensor& x, const c10::optional<Tensor>& idx, const Tensor& w,
                    const Tensor& wm, const Tensor& w16, const Tensor& w16t, const c10::optional<Tensor>& bias,
                    const c10::optional<Tensor>& bm, const Tensor& lr, double momentum) {
@@ -165,6 +184,10 @@ void xent_small(const Tensor& logits, const Tensor& y, const c10::optional<Tenso
 
 void register_mlp(py::module& m) {
   m.def("lin_fwd", &lin_fwd, "fused linear (+bias, +ReLU or ReLU-derivative mask), optional row gather");
+  m.def("lin_fwd_splitk", &lin_fwd_splitk,
+        "fused linear (+bias, +ReLU) for K >> M: slabs of LIN_SPLITK_KS columns into fp32 partials, summed in order");
+  m.def("lin_splitk_part_size", &splitk_part_size, "fp32 elements of lin_fwd_splitk's partial buffer for (M, N, K)");
+  m.attr("LIN_SPLITK_KS") = M_::SPLITK_KS;
   m.def("lin_wgrad_sgd", &lin_wgrad_sgd, "weight/bias gradient with fused SGD-momentum update");
   m.def("lin_wgrad_adam", &lin_wgrad_adam, "weight/bias gradient with fused Adam update (t = step_t[0], 1-based)");
   m.def("lin_wgrad_ftrl", &lin_wgrad_ftrl, "weight/bias gradient with fused FTRL-proximal update");
