@@ -1,4 +1,4 @@
-"""Cost of the fused dropout of the GPT-2 PBT member (csrc/hip/transformer_drop.hip) on one GPU.
+"""Cost of the fused dropout of the GPT-2 PBT member (csrc/hip/transformer.hip) on one GPU.
 
 1. The residual-add LayerNorm forward and backward at the member's batch (M = 16384 rows, D = 768),
    graph-captured and warmed, timed with HIP events: the existing kernels (p = 0) against the

@@ -1,7 +1,8 @@
 // Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): the
-// counter-based generator behind every dropout mask of the GPT-2 trial (transformer_drop.hip: the
-// LayerNorm and embedding sites; transformer.hip: the attention probabilities). ops/transformer.py
-// holds the same function in integer torch arithmetic, the oracle of the tests.
+// counter-based generator behind every dropout mask of the GPT-2 trial (transformer.hip: the
+// LayerNorm and embedding sites, contract above drop_words; the attention probabilities, contract
+// above attn_tile_words). ops/transformer.py holds the same function in integer torch arithmetic,
+// the oracle of the tests.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

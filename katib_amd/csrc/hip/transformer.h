@@ -26,7 +26,7 @@ hipError_t ln_bwd(const bf16* dy, const float* xin, const float* mean, const flo
 hipError_t ln_reduce_params(const float* part_g, const float* part_b, int nblk, int D, bf16* dgamma, bf16* dbeta,
                             hipStream_t st, const float* part_r = nullptr, bf16* dbias = nullptr);
 
-// Dropout fused into the residual LayerNorm kernels (transformer_drop.hip). The keep mask is never
+// Dropout fused into the residual LayerNorm kernels (their DROP instantiations). The keep mask is never
 // stored: element e = row * D + col of a site's [M, D] tensor takes word e & 3 of
 // Philox4x32-10(counter = (q lo, q hi, site, step), key = (seed lo, seed hi)), q = e >> 2, is kept
 // iff word >= thr = round(p * 2^32) and is then multiplied by scale = 1 / (1 - p). step is a device

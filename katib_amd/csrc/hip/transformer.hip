@@ -7,6 +7,9 @@
 //
 //  * ln_fwd / ln_bwd        residual add fused into LayerNorm; one wave per row, the row
 //                           in registers (D % 256 == 0), fp32 residual stream, bf16 out.
+//                           The <V, true> instantiations (ln_fwd_drop / ln_bwd_drop) drop the
+//                           residual branch: Philox keep mask on r going in, on dr going out.
+//  * dropout_f32 / _mask    the same mask over an fp32 tensor (embedding), and as bytes (tests).
 //  * gelu_fwd / gelu_bwd    tanh GELU, 16-byte vectors.
 //  * xent_fwd / xent_bwd    cross-entropy over the (padded) vocabulary straight from the
 //                           bf16 logits: online max/sum in the forward, the gradient
@@ -58,17 +61,80 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// ============================================================== residual / embedding dropout
+// Every residual-branch output of the flat model (attention proj, MLP fc2) is read once, by the
+// residual-add + LayerNorm forward, and its gradient is written once, as the dr output of the
+// LayerNorm backward. Dropout on those tensors therefore costs no launch and no memory traffic: the
+// <V, true> instantiations of ln_fwd_k / ln_bwd_k apply the keep mask to r on the way in and to dr
+// on the way out. Nothing is stored: both directions recompute the mask from a counter-based
+// generator, Philox4x32-10 (philox.h), keyed by
+//
+//     counter = (q & 0xffffffff, q >> 32, site, step),   key = (seed & 0xffffffff, seed >> 32)
+//
+// for the element index e = row * D + col of a row-major [M, D] tensor with q = e >> 2 (64-bit);
+// the element takes output word e & 3 and is kept iff word >= thr = round(p * 2^32); kept values
+// are multiplied by scale = 1 / (1 - p). A lane of the LayerNorm kernels owns columns
+// 256 i + 4 lane .. + 3, so one Philox call serves exactly one f32x4. `step` is read from device
+// memory (the model's optimizer step counter, fp32 like the AdamW kernel reads it), never passed by
+// value: a replayed HIP graph draws a fresh mask every step, and the forward and the backward of
+// one step see the same value because the counter advances after the backward.
+//
+// ops/transformer.py holds the same generator in integer torch arithmetic (the oracle of the tests).
+// The tests cannot reach the high counter word at their shapes (q >= 2^32 needs 2^34 elements);
+// q is formed in 64 bits here and there in the same way: (int64 row * D + col) >> 2.
+//
+//  * dropout_f32_k   in place over an fp32 [M, D] tensor (the embedding sum and its gradient).
+//  * dropout_mask_k  the keep mask itself as bytes (tests only), from the same device function.
+
+// The four random words of elements e .. e + 3 (e % 4 == 0) of a dropout site at this step.
+__device__ __forceinline__ u32x4 drop_words(int64_t e, const DropSpec& dp, uint32_t step) {
+  const uint64_t q = (uint64_t)e >> 2;
+  return philox4x32_10(u32x4{(uint32_t)q, (uint32_t)(q >> 32), dp.site, step}, (uint32_t)dp.seed,
+                       (uint32_t)(dp.seed >> 32));
+}
+__device__ __forceinline__ uint32_t drop_step(const DropSpec& dp) { return (uint32_t)*dp.step; }
+
+// one f32x4 (= one Philox call) per thread; n4 = number of f32x4
+__global__ __launch_bounds__(256) void dropout_f32_k(float* __restrict__ x, int64_t n4, const DropSpec dp) {
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (q >= n4) return;
+  const u32x4 w = drop_words(4 * q, dp, drop_step(dp));
+  f32x4 t = *reinterpret_cast<const f32x4*>(x + 4 * q);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) t[k] = w[k] >= dp.thr ? dp.scale * t[k] : 0.f;
+  *reinterpret_cast<f32x4*>(x + 4 * q) = t;
+}
+
+// four mask bytes (1 = keep) per thread, written as one 32-bit word
+__global__ __launch_bounds__(256) void dropout_mask_k(uint32_t* __restrict__ out, int64_t n4, const DropSpec dp) {
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (q >= n4) return;
+  const u32x4 w = drop_words(4 * q, dp, drop_step(dp));
+  uint32_t m = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) m |= (w[k] >= dp.thr ? 1u : 0u) << (8 * k);
+  out[q] = m;
+}
+
 // ============================================================== LayerNorm
-template <int V>  // D = 256 * V; one wave per row, lane owns columns 256 i + 4 lane .. + 3
+// The trailing kernel arguments `DP... dp` are the site's one DropSpec for DROP and nothing otherwise, so
+// the <V, false> instantiations have the arguments, instructions and descriptor they had before DROP existed.
+__device__ __forceinline__ const DropSpec& drop_of(const DropSpec& dp) { return dp; }
+
+// DROP: r is required and xo = x32 + (keep ? scale * r : 0).
+template <int V, bool DROP, class... DP>  // D = 256 * V; one wave per row, lane owns columns 256 i + 4 lane .. + 3
 __global__ __launch_bounds__(256) void ln_fwd_k(const float* __restrict__ x32, const u16* __restrict__ r,
                                                 float* __restrict__ xo, const u16* __restrict__ gamma,
                                                 const u16* __restrict__ beta, u16* __restrict__ y,
                                                 float* __restrict__ mean, float* __restrict__ rstd, int M,
-                                                float eps) {
+                                                float eps, const DP... dp) {
+  static_assert(sizeof...(DP) == (DROP ? 1 : 0), "one DropSpec for DROP, no argument otherwise");
   constexpr int D = 256 * V;
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= M) return;
+  [[maybe_unused]] uint32_t step = 0;
+  if constexpr (DROP) step = drop_step(dp...);
   const int64_t base = (int64_t)row * D;
   f32x4 v[V];
   float s = 0.f;
@@ -76,12 +142,21 @@ __global__ __launch_bounds__(256) void ln_fwd_k(const float* __restrict__ x32, c
   for (int i = 0; i < V; ++i) {
     const int c = 256 * i + 4 * lane;
     f32x4 t = *reinterpret_cast<const f32x4*>(x32 + base + c);
-    if (r) {
+    if (DROP || r) {
       const u32x2 rr = *reinterpret_cast<const u32x2*>(r + base + c);
-      t[0] += lo2f(rr[0]);
-      t[1] += hi2f(rr[0]);
-      t[2] += lo2f(rr[1]);
-      t[3] += hi2f(rr[1]);
+      if constexpr (DROP) {
+        const DropSpec& d = drop_of(dp...);
+        const u32x4 w = drop_words(base + c, d, step);
+        const f32x4 rv = f32x4{lo2f(rr[0]), hi2f(rr[0]), lo2f(rr[1]), hi2f(rr[1])};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (w[k] >= d.thr) t[k] += d.scale * rv[k];
+      } else {
+        t[0] += lo2f(rr[0]);
+        t[1] += hi2f(rr[0]);
+        t[2] += lo2f(rr[1]);
+        t[3] += hi2f(rr[1]);
+      }
       *reinterpret_cast<f32x4*>(xo + base + c) = t;
     }
     v[i] = t;
@@ -115,15 +190,22 @@ __global__ __launch_bounds__(256) void ln_fwd_k(const float* __restrict__ x32, c
 
 constexpr int kLnBwdBlocks = 256;
 
-template <int V>
+// DROP: dr is required and carries the mask of the branch whose output gradient it is: dx (the
+// residual-stream gradient) is unchanged, dr = keep ? bf16(scale * dx) : 0, and part_r sums those
+// bf16 values.
+template <int V, bool DROP, class... DP>
 __global__ __launch_bounds__(256) void ln_bwd_k(const u16* __restrict__ dy, const float* __restrict__ xin,
                                                 const float* __restrict__ mean, const float* __restrict__ rstd,
                                                 const u16* __restrict__ gamma, const float* dres, float* dx,
                                                 u16* __restrict__ dr, float* __restrict__ part_g,
-                                                float* __restrict__ part_b, float* __restrict__ part_r, int M) {
+                                                float* __restrict__ part_b, float* __restrict__ part_r, int M,
+                                                const DP... dp) {
+  static_assert(sizeof...(DP) == (DROP ? 1 : 0), "one DropSpec for DROP, no argument otherwise");
   constexpr int D = 256 * V;
   __shared__ float red[2][4][D];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  [[maybe_unused]] uint32_t step = 0;
+  if constexpr (DROP) step = drop_step(dp...);
   // part_r != nullptr: also the column sums of the bf16 gradient written to dr - the bias gradient
   // of the linear layer whose output dr is (GPT-2: attn proj / fc2), so no separate column-sum pass
   f32x4 ag[V], ab[V], ar[V], gv[V];
@@ -195,7 +277,15 @@ __global__ __launch_bounds__(256) void ln_bwd_k(const u16* __restrict__ dy, cons
         for (int k = 0; k < 4; ++k) o[k] = rs[r] * (g[r][i][k] * gv[i][k] - s1[r] - xh[r][i][k] * s2[r]);
         o += rd[r][i];
         *reinterpret_cast<f32x4*>(dx + base + c) = o;
-        if (dr) {
+        if (DROP || dr) {
+          if constexpr (DROP) {
+            // each f32x4's random words are generated right before its store, so they are never live
+            // across the two rows the wave holds in registers
+            const DropSpec& d = drop_of(dp...);
+            const u32x4 wd = drop_words(base + c, d, step);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = wd[k] >= d.thr ? d.scale * o[k] : 0.f;
+          }
           const u32x2 ob = u32x2{pack2(o[0], o[1]), pack2(o[2], o[3])};
           *reinterpret_cast<u32x2*>(dr + base + c) = ob;
           if (part_r) ar[i] += f32x4{lo2f(ob[0]), hi2f(ob[0]), lo2f(ob[1]), hi2f(ob[1])};  // what colsum(dr) sums
@@ -1213,10 +1303,10 @@ inline int grid_for(int64_t n, int per_thread) {
   return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
 }
 
-}  // namespace
-
-hipError_t ln_fwd(const float* x32, const bf16* r, float* xo, const bf16* gamma, const bf16* beta, bf16* y,
-                  float* mean, float* rstd, int M, int D, float eps, hipStream_t st) {
+// dp: the one DropSpec of the DROP form, nothing for the plain one
+template <bool DROP, class... DP>
+hipError_t ln_fwd_t(const float* x32, const bf16* r, float* xo, const bf16* gamma, const bf16* beta, bf16* y,
+                    float* mean, float* rstd, int M, int D, float eps, hipStream_t st, const DP&... dp) {
   const dim3 grid((M + 3) / 4), blk(256);
   const u16* rr = reinterpret_cast<const u16*>(r);
   const u16* gg = reinterpret_cast<const u16*>(gamma);
@@ -1224,12 +1314,49 @@ hipError_t ln_fwd(const float* x32, const bf16* r, float* xo, const bf16* gamma,
   u16* yy = reinterpret_cast<u16*>(y);
   switch (D / 256) {
 #define LN_CASE(V) \
-  case V: hipLaunchKernelGGL(ln_fwd_k<V>, grid, blk, 0, st, x32, rr, xo, gg, bb, yy, mean, rstd, M, eps); break;
+  case V:          \
+    hipLaunchKernelGGL((ln_fwd_k<V, DROP, DP...>), grid, blk, 0, st, x32, rr, xo, gg, bb, yy, mean, rstd, M, eps, \
+                       dp...);                                                                           \
+    break;
     LN_CASE(1) LN_CASE(2) LN_CASE(3) LN_CASE(4) LN_CASE(5) LN_CASE(6) LN_CASE(8)
 #undef LN_CASE
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
+}
+
+template <bool DROP, class... DP>
+hipError_t ln_bwd_t(const bf16* dy, const float* xin, const float* mean, const float* rstd, const bf16* gamma,
+                    const float* dres, float* dx, bf16* dr, float* part_g, float* part_b, int M, int D,
+                    hipStream_t st, float* part_r, const DP&... dp) {
+  const dim3 grid(ln_bwd_blocks(M)), blk(256);
+  const u16* d = reinterpret_cast<const u16*>(dy);
+  const u16* gg = reinterpret_cast<const u16*>(gamma);
+  u16* rr = reinterpret_cast<u16*>(dr);
+  switch (D / 256) {
+#define LN_CASE(V) \
+  case V:          \
+    hipLaunchKernelGGL((ln_bwd_k<V, DROP, DP...>), grid, blk, 0, st, d, xin, mean, rstd, gg, dres, dx, rr, part_g, \
+                       part_b, part_r, M, dp...);                                                              \
+    break;
+    LN_CASE(1) LN_CASE(2) LN_CASE(3) LN_CASE(4) LN_CASE(5) LN_CASE(6) LN_CASE(8)
+#undef LN_CASE
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t ln_fwd(const float* x32, const bf16* r, float* xo, const bf16* gamma, const bf16* beta, bf16* y,
+                  float* mean, float* rstd, int M, int D, float eps, hipStream_t st) {
+  return ln_fwd_t<false>(x32, r, xo, gamma, beta, y, mean, rstd, M, D, eps, st);
+}
+
+hipError_t ln_fwd_drop(const float* x32, const bf16* r, float* xo, const bf16* gamma, const bf16* beta, bf16* y,
+                       float* mean, float* rstd, int M, int D, float eps, const DropSpec& dp, hipStream_t st) {
+  if (r == nullptr || xo == nullptr || dp.step == nullptr) return hipErrorInvalidValue;
+  return ln_fwd_t<true>(x32, r, xo, gamma, beta, y, mean, rstd, M, D, eps, st, dp);
 }
 
 // (one workgroup per CU: the partial rows stay few for ln_reduce_k; each wave keeps two rows in flight,
@@ -1239,19 +1366,27 @@ int ln_bwd_blocks(int M) { return (M + 3) / 4 < kLnBwdBlocks ? (M + 3) / 4 : kLn
 hipError_t ln_bwd(const bf16* dy, const float* xin, const float* mean, const float* rstd, const bf16* gamma,
                   const float* dres, float* dx, bf16* dr, float* part_g, float* part_b, int M, int D,
                   hipStream_t st, float* part_r) {
-  const dim3 grid(ln_bwd_blocks(M)), blk(256);
-  const u16* d = reinterpret_cast<const u16*>(dy);
-  const u16* gg = reinterpret_cast<const u16*>(gamma);
-  u16* rr = reinterpret_cast<u16*>(dr);
-  switch (D / 256) {
-#define LN_CASE(V) \
-  case V:          \
-    hipLaunchKernelGGL(ln_bwd_k<V>, grid, blk, 0, st, d, xin, mean, rstd, gg, dres, dx, rr, part_g, part_b, part_r, M); \
-    break;
-    LN_CASE(1) LN_CASE(2) LN_CASE(3) LN_CASE(4) LN_CASE(5) LN_CASE(6) LN_CASE(8)
-#undef LN_CASE
-    default: return hipErrorInvalidValue;
-  }
+  return ln_bwd_t<false>(dy, xin, mean, rstd, gamma, dres, dx, dr, part_g, part_b, M, D, st, part_r);
+}
+
+hipError_t ln_bwd_drop(const bf16* dy, const float* xin, const float* mean, const float* rstd, const bf16* gamma,
+                       const float* dres, float* dx, bf16* dr, float* part_g, float* part_b, int M, int D,
+                       const DropSpec& dp, hipStream_t st, float* part_r) {
+  if (dr == nullptr || dp.step == nullptr) return hipErrorInvalidValue;
+  return ln_bwd_t<true>(dy, xin, mean, rstd, gamma, dres, dx, dr, part_g, part_b, M, D, st, part_r, dp);
+}
+
+hipError_t dropout_f32(float* x, int64_t n, const DropSpec& dp, hipStream_t st) {
+  const int64_t n4 = n / 4, blocks = (n4 + 255) / 256;
+  if (n <= 0 || n % 4 != 0 || blocks >= (1ll << 31) || dp.step == nullptr) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dropout_f32_k, dim3((unsigned)blocks), dim3(256), 0, st, x, n4, dp);
+  return hipGetLastError();
+}
+
+hipError_t dropout_mask(uint8_t* out, int64_t n, const DropSpec& dp, hipStream_t st) {
+  const int64_t n4 = n / 4, blocks = (n4 + 255) / 256;
+  if (n <= 0 || n % 4 != 0 || blocks >= (1ll << 31) || dp.step == nullptr) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dropout_mask_k, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<uint32_t*>(out), n4, dp);
   return hipGetLastError();
 }
 

@@ -26,11 +26,37 @@ void chk(const Tensor& t, at::ScalarType dt, int64_t numel, const char* name) {
 T_::bf16* bp(const Tensor& t) { return reinterpret_cast<T_::bf16*>(t.data_ptr()); }
 void ok(hipError_t e, const char* what) { TORCH_CHECK(e == hipSuccess, what, ": ", hipGetErrorString(e)); }
 
-void ln_fwd(const Tensor& x32, const c10::optional<Tensor>& r, const c10::optional<Tensor>& xo, const Tensor& gamma,
-            const Tensor& beta, const Tensor& y, const Tensor& mean, const Tensor& rstd, double eps) {
+// dropout site description shared by the four dropout entry points (transformer.h DropSpec)
+T_::DropSpec drop_spec(double p, int64_t site, int64_t seed, const Tensor& step) {
+  TORCH_CHECK(p >= 0.0 && p <= 0.9, "dropout: p must be in [0, 0.9], got ", p);
+  TORCH_CHECK(site >= 0 && site < (1ll << 32), "dropout: site must fit 32 bits");
+  TORCH_CHECK(seed >= 0, "dropout: seed must be non-negative");
+  TORCH_CHECK(step.is_cuda() && step.scalar_type() == at::kFloat && step.numel() == 1,
+              "dropout: step must be an fp32[1] GPU tensor");
+  T_::DropSpec dp;
+  dp.step = step.data_ptr<float>();
+  dp.seed = (uint64_t)seed;
+  dp.site = (uint32_t)site;
+  dp.thr = (uint32_t)std::floor(p * 4294967296.0 + 0.5);
+  dp.scale = 1.0f / (1.0f - (float)p);
+  return dp;
+}
+
+// what a *_drop entry point is given; the DropSpec is made of it after the tensor checks, as before
+struct DropArgs {
+  double p;
+  int64_t site, seed;
+  const Tensor& step;
+  T_::DropSpec spec() const { return drop_spec(p, site, seed, step); }
+};
+
+// the checked body of ln_fwd (da == nullptr) and ln_fwd_drop; `name` is the entry's, for its messages
+void ln_fwd_impl(const char* name, const Tensor& x32, const c10::optional<Tensor>& r, const c10::optional<Tensor>& xo,
+                 const Tensor& gamma, const Tensor& beta, const Tensor& y, const Tensor& mean, const Tensor& rstd,
+                 double eps, const DropArgs* da) {
   TORCH_CHECK(x32.dim() == 2, "x32 must be [M, D]");
   const int64_t M = x32.size(0), D = x32.size(1);
-  TORCH_CHECK(D % 256 == 0 && D / 256 >= 1 && D / 256 <= 8 && D / 256 != 7, "ln_fwd: D must be 256*{1..6,8}");
+  TORCH_CHECK(D % 256 == 0 && D / 256 >= 1 && D / 256 <= 8 && D / 256 != 7, name, ": D must be 256*{1..6,8}");
   chk(x32, at::kFloat, M * D, "x32");
   chk(gamma, at::kBFloat16, D, "gamma");
   chk(beta, at::kBFloat16, D, "beta");
@@ -40,25 +66,43 @@ void ln_fwd(const Tensor& x32, const c10::optional<Tensor>& r, const c10::option
   const T_::bf16* rp = nullptr;
   float* xop = nullptr;
   if (r.has_value()) {
-    TORCH_CHECK(xo.has_value(), "ln_fwd: residual add needs xo");
+    TORCH_CHECK(xo.has_value(), name, ": residual add needs xo");
     chk(*r, at::kBFloat16, M * D, "r");
     chk(*xo, at::kFloat, M * D, "xo");
     rp = bp(*r);
     xop = xo->data_ptr<float>();
   }
-  ok(T_::ln_fwd(x32.data_ptr<float>(), rp, xop, bp(gamma), bp(beta), bp(y), mean.data_ptr<float>(),
-                rstd.data_ptr<float>(), (int)M, (int)D, (float)eps, stream()),
-     "ln_fwd");
+  float* mp = mean.data_ptr<float>();
+  float* sp = rstd.data_ptr<float>();
+  ok(da ? T_::ln_fwd_drop(x32.data_ptr<float>(), rp, xop, bp(gamma), bp(beta), bp(y), mp, sp, (int)M, (int)D,
+                          (float)eps, da->spec(), stream())
+        : T_::ln_fwd(x32.data_ptr<float>(), rp, xop, bp(gamma), bp(beta), bp(y), mp, sp, (int)M, (int)D, (float)eps,
+                     stream()),
+     name);
+}
+
+void ln_fwd(const Tensor& x32, const c10::optional<Tensor>& r, const c10::optional<Tensor>& xo, const Tensor& gamma,
+            const Tensor& beta, const Tensor& y, const Tensor& mean, const Tensor& rstd, double eps) {
+  ln_fwd_impl("ln_fwd", x32, r, xo, gamma, beta, y, mean, rstd, eps, nullptr);
+}
+
+void ln_fwd_drop(const Tensor& x32, const Tensor& r, const Tensor& xo, const Tensor& gamma, const Tensor& beta,
+                 const Tensor& y, const Tensor& mean, const Tensor& rstd, double eps, double p, int64_t site,
+                 int64_t seed, const Tensor& step) {
+  const DropArgs da{p, site, seed, step};
+  ln_fwd_impl("ln_fwd_drop", x32, r, xo, gamma, beta, y, mean, rstd, eps, &da);
 }
 
 int64_t ln_bwd_blocks(int64_t M) { return T_::ln_bwd_blocks((int)M); }
 
-void ln_bwd(const Tensor& dy, const Tensor& xin, const Tensor& mean, const Tensor& rstd, const Tensor& gamma,
-            const c10::optional<Tensor>& dres, const Tensor& dx, const c10::optional<Tensor>& dr,
-            const Tensor& part_g, const Tensor& part_b, const c10::optional<Tensor>& part_r) {
+// the checked body of ln_bwd (da == nullptr) and ln_bwd_drop
+void ln_bwd_impl(const char* name, const Tensor& dy, const Tensor& xin, const Tensor& mean, const Tensor& rstd,
+                 const Tensor& gamma, const c10::optional<Tensor>& dres, const Tensor& dx,
+                 const c10::optional<Tensor>& dr, const Tensor& part_g, const Tensor& part_b,
+                 const c10::optional<Tensor>& part_r, const DropArgs* da) {
   TORCH_CHECK(xin.dim() == 2, "xin must be [M, D]");
   const int64_t M = xin.size(0), D = xin.size(1);
-  TORCH_CHECK(D % 256 == 0 && D / 256 >= 1 && D / 256 <= 8 && D / 256 != 7, "ln_bwd: D must be 256*{1..6,8}");
+  TORCH_CHECK(D % 256 == 0 && D / 256 >= 1 && D / 256 <= 8 && D / 256 != 7, name, ": D must be 256*{1..6,8}");
   chk(dy, at::kBFloat16, M * D, "dy");
   chk(xin, at::kFloat, M * D, "xin");
   chk(mean, at::kFloat, M, "mean");
@@ -80,84 +124,33 @@ void ln_bwd(const Tensor& dy, const Tensor& xin, const Tensor& mean, const Tenso
   }
   float* prp = nullptr;
   if (part_r.has_value()) {
-    TORCH_CHECK(drp != nullptr, "ln_bwd: part_r (bias-gradient column sums of dr) needs dr");
+    TORCH_CHECK(drp != nullptr, name, ": part_r (bias-gradient column sums of dr) needs dr");
     chk(*part_r, at::kFloat, nb * D, "part_r");
     prp = part_r->data_ptr<float>();
   }
-  ok(T_::ln_bwd(bp(dy), xin.data_ptr<float>(), mean.data_ptr<float>(), rstd.data_ptr<float>(), bp(gamma), dresp,
-                dx.data_ptr<float>(), drp, part_g.data_ptr<float>(), part_b.data_ptr<float>(), (int)M, (int)D,
-                stream(), prp),
-     "ln_bwd");
+  const float* mp = mean.data_ptr<float>();
+  const float* sp = rstd.data_ptr<float>();
+  float* pg = part_g.data_ptr<float>();
+  float* pb = part_b.data_ptr<float>();
+  ok(da ? T_::ln_bwd_drop(bp(dy), xin.data_ptr<float>(), mp, sp, bp(gamma), dresp, dx.data_ptr<float>(), drp, pg, pb,
+                          (int)M, (int)D, da->spec(), stream(), prp)
+        : T_::ln_bwd(bp(dy), xin.data_ptr<float>(), mp, sp, bp(gamma), dresp, dx.data_ptr<float>(), drp, pg, pb,
+                     (int)M, (int)D, stream(), prp),
+     name);
 }
 
-// dropout site description shared by the four dropout entry points (transformer.h DropSpec)
-T_::DropSpec drop_spec(double p, int64_t site, int64_t seed, const Tensor& step) {
-  TORCH_CHECK(p >= 0.0 && p <= 0.9, "dropout: p must be in [0, 0.9], got ", p);
-  TORCH_CHECK(site >= 0 && site < (1ll << 32), "dropout: site must fit 32 bits");
-  TORCH_CHECK(seed >= 0, "dropout: seed must be non-negative");
-  TORCH_CHECK(step.is_cuda() && step.scalar_type() == at::kFloat && step.numel() == 1,
-              "dropout: step must be an fp32[1] GPU tensor");
-  T_::DropSpec dp;
-  dp.step = step.data_ptr<float>();
-  dp.seed = (uint64_t)seed;
-  dp.site = (uint32_t)site;
-  dp.thr = (uint32_t)std::floor(p * 4294967296.0 + 0.5);
-  dp.scale = 1.0f / (1.0f - (float)p);
-  return dp;
-}
-
-void ln_fwd_drop(const Tensor& x32, const Tensor& r, const Tensor& xo, const Tensor& gamma, const Tensor& beta,
-                 const Tensor& y, const Tensor& mean, const Tensor& rstd, double eps, double p, int64_t site,
-                 int64_t seed, const Tensor& step) {
-  TORCH_CHECK(x32.dim() == 2, "x32 must be [M, D]");
-  const int64_t M = x32.size(0), D = x32.size(1);
-  TORCH_CHECK(D % 256 == 0 && D / 256 >= 1 && D / 256 <= 8 && D / 256 != 7, "ln_fwd_drop: D must be 256*{1..6,8}");
-  chk(x32, at::kFloat, M * D, "x32");
-  chk(gamma, at::kBFloat16, D, "gamma");
-  chk(beta, at::kBFloat16, D, "beta");
-  chk(y, at::kBFloat16, M * D, "y");
-  chk(mean, at::kFloat, M, "mean");
-  chk(rstd, at::kFloat, M, "rstd");
-  chk(r, at::kBFloat16, M * D, "r");
-  chk(xo, at::kFloat, M * D, "xo");
-  const T_::DropSpec dp = drop_spec(p, site, seed, step);
-  ok(T_::ln_fwd_drop(x32.data_ptr<float>(), bp(r), xo.data_ptr<float>(), bp(gamma), bp(beta), bp(y),
-                     mean.data_ptr<float>(), rstd.data_ptr<float>(), (int)M, (int)D, (float)eps, dp, stream()),
-     "ln_fwd_drop");
+void ln_bwd(const Tensor& dy, const Tensor& xin, const Tensor& mean, const Tensor& rstd, const Tensor& gamma,
+            const c10::optional<Tensor>& dres, const Tensor& dx, const c10::optional<Tensor>& dr,
+            const Tensor& part_g, const Tensor& part_b, const c10::optional<Tensor>& part_r) {
+  ln_bwd_impl("ln_bwd", dy, xin, mean, rstd, gamma, dres, dx, dr, part_g, part_b, part_r, nullptr);
 }
 
 void ln_bwd_drop(const Tensor& dy, const Tensor& xin, const Tensor& mean, const Tensor& rstd, const Tensor& gamma,
                  const c10::optional<Tensor>& dres, const Tensor& dx, const Tensor& dr, const Tensor& part_g,
                  const Tensor& part_b, const c10::optional<Tensor>& part_r, double p, int64_t site, int64_t seed,
                  const Tensor& step) {
-  TORCH_CHECK(xin.dim() == 2, "xin must be [M, D]");
-  const int64_t M = xin.size(0), D = xin.size(1);
-  TORCH_CHECK(D % 256 == 0 && D / 256 >= 1 && D / 256 <= 8 && D / 256 != 7, "ln_bwd_drop: D must be 256*{1..6,8}");
-  chk(dy, at::kBFloat16, M * D, "dy");
-  chk(xin, at::kFloat, M * D, "xin");
-  chk(mean, at::kFloat, M, "mean");
-  chk(rstd, at::kFloat, M, "rstd");
-  chk(gamma, at::kBFloat16, D, "gamma");
-  chk(dx, at::kFloat, M * D, "dx");
-  chk(dr, at::kBFloat16, M * D, "dr");
-  const int64_t nb = T_::ln_bwd_blocks((int)M);
-  chk(part_g, at::kFloat, nb * D, "part_g");
-  chk(part_b, at::kFloat, nb * D, "part_b");
-  const float* dresp = nullptr;
-  if (dres.has_value()) {
-    chk(*dres, at::kFloat, M * D, "dres");
-    dresp = dres->data_ptr<float>();
-  }
-  float* prp = nullptr;
-  if (part_r.has_value()) {
-    chk(*part_r, at::kFloat, nb * D, "part_r");
-    prp = part_r->data_ptr<float>();
-  }
-  const T_::DropSpec dp = drop_spec(p, site, seed, step);
-  ok(T_::ln_bwd_drop(bp(dy), xin.data_ptr<float>(), mean.data_ptr<float>(), rstd.data_ptr<float>(), bp(gamma), dresp,
-                     dx.data_ptr<float>(), bp(dr), part_g.data_ptr<float>(), part_b.data_ptr<float>(), (int)M, (int)D,
-                     dp, stream(), prp),
-     "ln_bwd_drop");
+  const DropArgs da{p, site, seed, step};
+  ln_bwd_impl("ln_bwd_drop", dy, xin, mean, rstd, gamma, dres, dx, dr, part_g, part_b, part_r, &da);
 }
 
 void dropout_f32(const Tensor& x, double p, int64_t site, int64_t seed, const Tensor& step) {

@@ -65,7 +65,7 @@ def _kern():
 
 
 # ---------------------------------------------------------------- dropout (Philox4x32-10)
-# The dropout mask of the GPT-2 trial is never stored: the kernels of csrc/hip/transformer_drop.hip and
+# The dropout mask of the GPT-2 trial is never stored: the kernels of csrc/hip/transformer.hip and
 # the torch oracle below recompute it, forward and backward, from the same counter-based generator.
 # For a site applied to a row-major [M, D] tensor, element e = row * D + col:
 #   q = e >> 2 (64-bit); counter = (q & 0xffffffff, q >> 32, site, step); key = (seed & 0xffffffff, seed >> 32);
@@ -406,7 +406,7 @@ class HipOps:
         self.k.gemm_nt(x, w, b, u, g)
         return u, g
 
-    # dropout (csrc/hip/transformer_drop.hip): the mask is recomputed by every kernel from Philox4x32-10
+    # dropout (csrc/hip/transformer.hip): the mask is recomputed by every kernel from Philox4x32-10
     # keyed by (site, seed, device step counter) - see the contract at the top of this module
     def dropout_mask(self, M, D, drop, device=None):
         step = drop.step

@@ -21,8 +21,8 @@ drops the embedding sum and every attention-proj / MLP-fc2 output while training
 (same range, an independent switch, ``examples/pbt/pbt-gpt2-small-attn-dropout.yaml``) drops the
 attention probabilities; evaluation never drops. The flat model's masks come from a
 counter-based generator keyed by ``--seed`` and the checkpointed step counter (fused into the
-LayerNorm kernels, ``csrc/hip/transformer_drop.hip``, and recomputed inside the flash attention
-kernels, ``csrc/hip/transformer.hip``), so a child that resumes a parent continues its mask stream;
+LayerNorm kernels and recomputed inside the flash attention kernels, both in
+``csrc/hip/transformer.hip``), so a child that resumes a parent continues its mask stream;
 the ``nn.Module`` path uses ``F.dropout`` and SDPA's ``dropout_p`` (statistically, not bitwise, the
 same). The attention site draws 8 bits per probability: its realised rate is ``round(256 p) / 256``
 and a ``p`` below 1/512 is no dropout.

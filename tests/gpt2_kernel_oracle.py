@@ -1,4 +1,4 @@
-"""References for the GPT-2 trial kernels (csrc/hip/transformer.hip, transformer_drop.hip) in plain
+"""References for the GPT-2 trial kernels (csrc/hip/transformer.hip) in plain
 torch, on any device, and the per-row checker the kernel tests judge them with.
 
 Two arms of every contract of ``katib_amd.ops.transformer`` on the same bf16-rounded inputs, each

@@ -1,4 +1,4 @@
-"""Dropout kernels of the GPT-2 trial (csrc/hip/transformer_drop.hip) against the torch oracle of the
+"""Dropout kernels of the GPT-2 trial (csrc/hip/transformer.hip) against the torch oracle of the
 same Philox4x32-10 contract (ops/transformer.py): the mask bit for bit, the fused LayerNorm forward /
 backward, the in-place fp32 kernel, a replayed graph drawing a fresh mask per step, a whole flat-model
 step and the graph-captured trial. Tolerances are those of tests/test_gpu_transformer.py."""

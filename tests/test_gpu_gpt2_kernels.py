@@ -1,4 +1,4 @@
-"""The GPT-2 trial kernels (csrc/hip/transformer.hip, transformer_drop.hip) against the fp64 oracle of
+"""The GPT-2 trial kernels (csrc/hip/transformer.hip) against the fp64 oracle of
 tests/gpt2_kernel_oracle.py, row by row, at the shapes where their loops, tails and path switches
 sit: the second row of a LayerNorm-backward wave and its second grid-stride iteration, the first
 element counts at which the flat kernels loop, both fused cross-entropy widths and the two-pass
@@ -181,6 +181,36 @@ def test_layernorm_dropout_rows_past_1024(hip):
     assert torch.equal(out["dr"] == 0, ~keep)
     assert torch.equal((out["dr"] == 0)[1024:], ~keep[1024:]) and not bool(keep[1024:].all())
     _ln_check_bwd("ln_bwd_drop", out, dy, xin, mean, rstd, gamma, G0, True, keep=keep, scale=scale)
+
+
+# (256, 5): the tail row of a workgroup; (256, 1029): the half-valid second row of a backward wave;
+# (2048, 5): the widest instantiation
+@pytest.mark.parametrize("D,M", [(256, 5), (256, 1029), (2048, 5)])
+def test_layernorm_drop_p0_is_plain(hip, D, M):
+    """The two branches of each LayerNorm template compute the same thing: at p = 0 (thr = 0 keeps
+    every element, scale = 1.0f, and t + 1.0 * r, 1.0 * o round as t + r, o, fused or not) the
+    dropped entry points, called straight through the binding, give the plain ones' bits."""
+    x, r, gamma, beta, dy, G0 = _ln_inputs(M, D)
+    step = torch.full((1,), 3.0, device=DEV)
+    nb = hip.k.ln_bwd_blocks(M)
+
+    def run(drop):  # outputs start as NaN, which equals nothing: an element left unwritten fails below
+        tail = (0.0, 5, SEED, step) if drop else ()
+        nan = float("nan")
+        xo, y = torch.full_like(x, nan), torch.full((M, D), nan, device=DEV, dtype=BF16)
+        mean, rstd = torch.full((M,), nan, device=DEV), torch.full((M,), nan, device=DEV)
+        (hip.k.ln_fwd_drop if drop else hip.k.ln_fwd)(x, r, xo, gamma, beta, y, mean, rstd, 1e-5, *tail)
+        G, dr = G0.clone(), torch.full((M, D), nan, device=DEV, dtype=BF16)
+        part = torch.full((3, nb, D), nan, device=DEV)
+        (hip.k.ln_bwd_drop if drop else hip.k.ln_bwd)(dy, xo, mean, rstd, gamma, G, G, dr, part[0], part[1], part[2],
+                                                      *tail)
+        return {"xo": xo, "y": y, "mean": mean, "rstd": rstd, "dx": G, "dr": dr, "part_g": part[0],
+                "part_b": part[1], "part_r": part[2]}
+
+    plain, dropped = run(False), run(True)
+    assert torch.equal(plain["xo"], x + r.float())
+    for k in plain:
+        assert torch.equal(dropped[k], plain[k]), k
 
 
 # ============================================================================== GELU
