@@ -103,7 +103,13 @@ def build_selftest(sanitize: str = "address,undefined", out_dir: str = "", verbo
 # darts_ops_fwd.hip / darts_ops_pwb.hip (DARTS pointwise MFMA): darts-gpu.yaml step 41.86 -> 40.71 ms, B5
 # neutral (profiles/darts_vgpr_form_ab_r05.log).
 _VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
-HIP_TU_FLAGS = {"transformer.hip": _VGPR_FORM, "darts_ops_fwd.hip": _VGPR_FORM, "darts_ops_pwb.hip": _VGPR_FORM}
+# New translation units are compiled with the packed fp32 VALU forms (v_pk_add / mul / fma_f32) off, so
+# that no later edit gets them from the vectoriser unasked. A guard, not a tuning: enas_concat.hip has
+# no fp32 arithmetic, and its gfx950 ISA and resource report are the same with and without the flag
+# (48 / 50, 44 / 24, 14 / 9 VGPRs, no scratch). The host pass does not know the feature and says so.
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+HIP_TU_FLAGS = {"transformer.hip": _VGPR_FORM, "darts_ops_fwd.hip": _VGPR_FORM, "darts_ops_pwb.hip": _VGPR_FORM,
+                "enas_concat.hip": _NO_PK_F32}
 
 
 def hip_target() -> str:

@@ -5,6 +5,7 @@
 #include <c10/hip/HIPStream.h>
 
 #include "dwconv.h"
+#include "enas_concat.h"
 #include "pool_nhwc.h"
 
 namespace py = pybind11;
@@ -126,9 +127,91 @@ void pool_bwd(const Tensor& gy, const c10::optional<Tensor>& arg, const Tensor& 
               "pool_bwd launch failed");
 }
 
+// ---- layer-input builder (enas_concat.hip): ReLU + zero-pad + concat of NHWC bf16 sources
+namespace EC = katib_hip::enasconcat;
+
+void concat_src(const Tensor& t, int64_t B, int64_t H, int64_t C, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16 && t.is_contiguous(), name,
+              " must be a contiguous bf16 GPU tensor");
+  TORCH_CHECK(t.dim() == 4 && t.size(0) == B && t.size(1) == H && t.size(2) == H && t.size(3) == C, name,
+              " must be [B, H, H, C] with a square map and the common batch size");
+}
+
+// xs[i] [B, H_i, H_i, C_i] -> out [B, m, m, sum C_i]
+void enas_concat_fwd(const std::vector<Tensor>& xs, const Tensor& out, bool relu) {
+  TORCH_CHECK(!xs.empty() && (int64_t)xs.size() <= EC::kMaxSrc, "enas_concat: 1 to ", EC::kMaxSrc, " sources, got ",
+              xs.size());
+  TORCH_CHECK(xs[0].dim() == 4, "enas_concat: sources are [B, H, H, C]");
+  EC::Table tb{};
+  tb.n = (int)xs.size();
+  tb.B = (int)xs[0].size(0);
+  for (int i = 0; i < tb.n; ++i) {
+    TORCH_CHECK(xs[i].dim() == 4 && xs[i].size(1) < (1 << 20) && xs[i].size(3) < (1 << 20), "enas_concat: bad source");
+    concat_src(xs[i], tb.B, xs[i].size(1), xs[i].size(3), "source");
+    TORCH_CHECK(xs[i].device() == out.device(), "enas_concat: tensors on different devices");
+    tb.s[i].x = xs[i].data_ptr();
+    tb.s[i].H = (int)xs[i].size(1);
+    tb.s[i].C = (int)xs[i].size(3);
+  }
+  TORCH_CHECK(EC::finish(tb, 0), "enas_concat: empty source or B * m * m * C >= 2^31");
+  concat_src(out, tb.B, tb.m, tb.Ct, "out");
+  TORCH_CHECK(EC::launch_fwd(tb, relu, out.data_ptr(), stream()) == hipSuccess, "enas_concat_fwd launch failed");
+}
+
+// geom[i] = (H_i, C_i); xs[i] (read only with relu) and gxs[i] [B, H_i, H_i, C_i], gxs[i] None where no
+// gradient is wanted; gout [B, m, m, Ct] whose pixels lie gs >= Ct elements apart
+void enas_concat_bwd(const std::vector<std::vector<int64_t>>& geom, int64_t B,
+                     const std::vector<c10::optional<Tensor>>& xs, const std::vector<c10::optional<Tensor>>& gxs,
+                     const Tensor& gout, bool relu) {
+  const size_t n = geom.size();
+  TORCH_CHECK(n >= 1 && (int64_t)n <= EC::kMaxSrc, "enas_concat: 1 to ", EC::kMaxSrc, " sources, got ", n);
+  TORCH_CHECK(xs.size() == n && gxs.size() == n && B >= 1 && B < (1ll << 31), "enas_concat_bwd: list lengths differ");
+  TORCH_CHECK(gout.is_cuda() && gout.scalar_type() == at::kBFloat16 && gout.dim() == 4, "gout must be 4-D bf16 on a GPU");
+  EC::Table tb{};
+  tb.n = (int)n;
+  tb.B = (int)B;
+  for (size_t i = 0; i < n; ++i) {
+    TORCH_CHECK(geom[i].size() == 2 && geom[i][0] >= 1 && geom[i][0] < (1 << 20) && geom[i][1] >= 1 &&
+                    geom[i][1] < (1 << 20), "enas_concat_bwd: geometry is (H, C) per source");
+    tb.s[i].H = (int)geom[i][0];
+    tb.s[i].C = (int)geom[i][1];
+    if (gxs[i].has_value() && gxs[i]->defined()) {
+      concat_src(*gxs[i], B, tb.s[i].H, tb.s[i].C, "gx");
+      TORCH_CHECK(gxs[i]->device() == gout.device(), "enas_concat: tensors on different devices");
+      tb.s[i].gx = gxs[i]->data_ptr();
+      if (relu) {
+        TORCH_CHECK(xs[i].has_value() && xs[i]->defined(), "enas_concat_bwd: ReLU needs the sources");
+        concat_src(*xs[i], B, tb.s[i].H, tb.s[i].C, "source");
+        TORCH_CHECK(xs[i]->device() == gout.device(), "enas_concat: tensors on different devices");
+        tb.s[i].x = xs[i]->data_ptr();
+      }
+    }
+  }
+  // the pixel stride, from the first dimension that has one (a dimension of size 1 has no say)
+  TORCH_CHECK(gout.size(3) == 1 || gout.stride(3) == 1, "gout channels must be adjacent");
+  int64_t gs = 0;
+  {
+    EC::Table probe = tb;
+    TORCH_CHECK(EC::finish(probe, 0), "enas_concat: B * m * m * C >= 2^31");
+    const int64_t m = probe.m;
+    TORCH_CHECK(gout.size(0) == B && gout.size(1) == m && gout.size(2) == m && gout.size(3) == probe.Ct,
+                "gout must be [B, m, m, Ct]");
+    gs = m > 1 ? gout.stride(2) : (B > 1 ? gout.stride(0) : probe.Ct);
+    TORCH_CHECK(gs >= probe.Ct && (m == 1 || gout.stride(1) == m * gs) && (B == 1 || gout.stride(0) == m * m * gs),
+                "gout must be dense up to a pixel stride >= Ct");
+    const int64_t last = (B * m * m - 1) * gs + probe.Ct;  // one past the last element read
+    TORCH_CHECK((gout.storage_offset() + last) * 2 <= (int64_t)gout.storage().nbytes(), "gout reaches past its storage");
+  }
+  TORCH_CHECK(EC::finish(tb, gs), "enas_concat: B * m * m * gs >= 2^31");
+  TORCH_CHECK(EC::launch_bwd(tb, relu, gout.data_ptr(), (int)gs, stream()) == hipSuccess, "enas_concat_bwd launch failed");
+}
+
 }  // namespace
 
 void register_dwconv(py::module& m) {
+  m.def("enas_concat_fwd", &enas_concat_fwd, "ReLU + zero-pad + channel concat of NHWC bf16 sources");
+  m.def("enas_concat_bwd", &enas_concat_bwd, "its backward: one gradient per source that wants one");
+  m.attr("ENAS_CONCAT_MAX_SRC") = EC::kMaxSrc;
   m.def("pool_nhwc_fwd", &pool_fwd, "max / avg pooling forward (NHWC bf16, valid padding)");
   m.def("pool_nhwc_bwd", &pool_bwd, "max / avg pooling backward (NHWC bf16, gather, no atomics)");
   m.def("dw_fwd", &dw_fwd, "depthwise conv forward (NHWC bf16)", py::arg("x"), py::arg("w"), py::arg("bias"),

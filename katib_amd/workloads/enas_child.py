@@ -18,9 +18,11 @@ depthwise convolutions on the NHWC depthwise kernels (``ops/dwconv.py``; the 3-c
 image input is zero-padded to 8 channels there, so no op falls back to MIOpen), batch norm
 on the NHWC bf16 HIP kernels (``ops/batchnorm.py``, channel counts that are multiples of
 8), max / average pooling of the ``reduction`` op on the NHWC bf16 pool kernels
-(``ops/pool.py``), synthetic CIFAR-10-shaped data in HBM, and data parallelism
-over the trial's GPUs (``WORLD_SIZE`` ranks, RCCL all-reduce of the flat gradient)
-in place of ``tf.distribute.MirroredStrategy``.
+(``ops/pool.py``), each layer's input - ReLU of the zero-pad concatenation of its sources -
+built by one kernel forward and one backward (``ops/enas_concat.py``; ``FUSED_INPUT``),
+synthetic CIFAR-10-shaped data in HBM, and data parallelism over the trial's GPUs
+(``WORLD_SIZE`` ranks, RCCL all-reduce of the flat gradient) in place of
+``tf.distribute.MirroredStrategy``.
 
 Data and augmentation (``RunTrial.py:71-96``). ``--data-dir DIR`` trains on the CIFAR-10 binary
 version found there (``workloads/data.py: cifar10_from_dir``; train split capped by ``--num-train``)
@@ -51,8 +53,16 @@ from ..ops import batchnorm as hbn
 from ..ops import conv as hconv
 from ..ops import pool as hpool
 from ..ops import dwconv as hdw
+from ..ops import enas_concat as hcat
 from ..ops.augment import PLAIN, AugSpec, augment_gather, cifar_lut
 from .common import CapturedStep, Timer, device, global_avg_pool, pattern_images, report
+
+
+# On: build a layer's input (pad, concat, ReLU) with the fused HIP kernels where they serve the
+# sources. Off: F.pad + torch.cat + F.relu. The op's values and gradients are the same either way.
+# Off until the captured step has been timed against the unfused one (ARCHITECTURE section 4,
+# profiles/enas_concat.log).
+FUSED_INPUT = False
 
 
 def _same_pad(size: int, k: int, s: int):
@@ -120,14 +130,14 @@ class Op(nn.Module):
         else:
             raise ValueError("unknown opt_type %r" % self.kind)
 
-    def forward(self, x):
+    def forward(self, x, relu_done=False):
         if self.kind == "reduction":
             if self.identity:
                 return x
             if hpool.supported(x, self.p, self.st):  # HIP NHWC bf16 pooling (no MIOpen in the graph)
                 return hpool.pool2d(x, self.p, self.st, self.is_max)
             return self.pool(x)
-        return self.body(F.relu(x))
+        return self.body(x if relu_done else F.relu(x))
 
 
 def _concat(xs: List[torch.Tensor]):
@@ -171,7 +181,12 @@ class ChildNet(nn.Module):
     def forward(self, x):
         layers = [x]
         for op, ins in zip(self.ops, self.inputs):
-            layers.append(op(_concat([layers[i] for i in ins])))
+            srcs = [layers[i] for i in ins]
+            pool = op.kind == "reduction"
+            if FUSED_INPUT and not (pool and len(srcs) == 1) and hcat.supported(srcs):
+                layers.append(op(hcat.relu_pad_concat(srcs, relu=not pool), relu_done=True))
+            else:
+                layers.append(op(_concat(srcs)))
         return self.fc(self.drop(global_avg_pool(layers[-1])))
 
 
