@@ -6,6 +6,7 @@
 
 #include "dwconv.h"
 #include "enas_concat.h"
+#include "enas_head.h"
 #include "pool_nhwc.h"
 
 namespace py = pybind11;
@@ -206,9 +207,112 @@ void enas_concat_bwd(const std::vector<std::vector<int64_t>>& geom, int64_t B,
   TORCH_CHECK(EC::launch_bwd(tb, relu, gout.data_ptr(), (int)gs, stream()) == hipSuccess, "enas_concat_bwd launch failed");
 }
 
+// ---- head of the child (enas_head.hip): pooling, dropout, dense, softmax cross-entropy
+namespace EH = katib_hip::enashead;
+
+void head_t(const Tensor& t, at::ScalarType ty, int64_t numel, const Tensor& on, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == ty && t.is_contiguous() && t.numel() == numel &&
+                  t.device() == on.device(),
+              "enas_head: ", name, " must be a contiguous tensor of ", numel, " elements on the activation's GPU");
+}
+
+void head_sizes(int64_t B, int64_t HW, int64_t C, int64_t K) {
+  TORCH_CHECK(B >= 1 && HW >= 1 && C >= 1 && K >= 1, "enas_head: empty tensor");
+  TORCH_CHECK(K <= EH::kMaxK, "enas_head: K = ", K, " classes, the kernels serve K <= ", EH::kMaxK);
+  TORCH_CHECK(C <= EH::kMaxC, "enas_head: C = ", C, " channels, the kernels serve C <= ", EH::kMaxC);
+  TORCH_CHECK(B * HW * C < (1ll << 31), "enas_head: B * H * W * C >= 2^31");
+}
+
+// x [B, H, W, C] bf16 dense. thr > 0: dropout with round(p 2^32) = thr and `scale`, the draw keyed by
+// (seed, site, *step). mean: out[0] = loss / B and *step += 1 (training); else the sum (evaluation).
+// Returns out [2] (loss, hits), feat, keep, logits, dl, loss_b, hit_b.
+std::vector<Tensor> enas_head_fwd(const Tensor& x, const Tensor& w, const Tensor& bias, const Tensor& y, int64_t thr,
+                                  double scale, int64_t site, int64_t seed_lo, int64_t seed_hi,
+                                  const c10::optional<Tensor>& step, bool mean, const c10::optional<Tensor>& stats) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 4 && x.is_contiguous(),
+              "enas_head: x must be a dense [B, H, W, C] bf16 GPU tensor");
+  TORCH_CHECK(w.dim() == 2, "enas_head: weight is [K, C]");
+  const int64_t B = x.size(0), HW = x.size(1) * x.size(2), C = x.size(3), K = w.size(0);
+  head_sizes(B, HW, C, K);
+  head_t(w, at::kFloat, K * C, x, "weight");
+  head_t(bias, at::kFloat, K, x, "bias");
+  head_t(y, at::kLong, B, x, "labels");
+  TORCH_CHECK(thr >= 0 && thr < (1ll << 32) && site >= 0 && site < (1ll << 32) && seed_lo >= 0 &&
+                  seed_lo < (1ll << 32) && seed_hi >= 0 && seed_hi < (1ll << 32), "enas_head: dropout words are 32-bit");
+  const bool has_step = step.has_value() && step->defined();
+  if (has_step) head_t(*step, at::kInt, 1, x, "step");
+  TORCH_CHECK(thr == 0 || has_step, "enas_head: dropout needs the device step counter");
+  const bool has_stats = stats.has_value() && stats->defined();
+  if (has_stats) head_t(*stats, at::kFloat, 2, x, "stats");
+  const auto f32 = x.options().dtype(at::kFloat);
+  Tensor out = at::empty({2}, f32), feat = at::empty({B, C}, f32), keep = at::empty({B, C}, x.options().dtype(at::kByte)),
+         logits = at::empty({B, K}, f32), dl = at::empty({B, K}, f32), loss_b = at::empty({B}, f32),
+         hit_b = at::empty({B}, f32);
+  EH::Fwd a{};
+  a.x = x.data_ptr();
+  a.w = w.data_ptr<float>();
+  a.bias = bias.data_ptr<float>();
+  a.y = y.data_ptr<int64_t>();
+  a.step = has_step ? step->data_ptr<int32_t>() : nullptr;
+  a.feat = feat.data_ptr<float>();
+  a.keep = keep.data_ptr<uint8_t>();
+  a.logits = logits.data_ptr<float>();
+  a.dl = dl.data_ptr<float>();
+  a.loss_b = loss_b.data_ptr<float>();
+  a.hit_b = hit_b.data_ptr<float>();
+  a.B = (int)B, a.HW = (int)HW, a.C = (int)C, a.K = (int)K;
+  a.seed = (uint64_t)seed_lo | ((uint64_t)seed_hi << 32);
+  a.site = (uint32_t)site, a.thr = (uint32_t)thr, a.scale = (float)scale;
+  TORCH_CHECK(EH::launch_fwd(a, thr > 0, stream()) == hipSuccess, "enas_head_fwd launch failed");
+  EH::Sum s{loss_b.data_ptr<float>(), hit_b.data_ptr<float>(), out.data_ptr<float>(),
+            has_stats ? stats->data_ptr<float>() : nullptr, mean && has_step ? step->data_ptr<int32_t>() : nullptr,
+            (int)B, mean ? 1 : 0};
+  TORCH_CHECK(EH::launch_sum(s, stream()) == hipSuccess, "enas_head_sum launch failed");
+  return {out, feat, keep, logits, dl, loss_b, hit_b};
+}
+
+// g: the loss's upstream gradient, one fp32 on the GPU. Returns dx [B, H, W, C] bf16, dW, db; an
+// undefined tensor where none is wanted. segs > 0 sets the data role's segments per sample (A/B).
+std::vector<Tensor> enas_head_bwd(const Tensor& g, const Tensor& dl, const Tensor& w, const Tensor& feat,
+                                  const Tensor& keep, int64_t H, int64_t W, double scale, bool need_dx, bool need_dw,
+                                  bool need_db, int64_t segs) {
+  TORCH_CHECK(dl.is_cuda() && dl.dim() == 2 && feat.dim() == 2 && H >= 1 && W >= 1 && H < (1 << 20) && W < (1 << 20),
+              "enas_head_bwd: dl [B, K], feat [B, C], H, W");
+  const int64_t B = dl.size(0), K = dl.size(1), C = feat.size(1), HW = H * W;
+  head_sizes(B, HW, C, K);
+  head_t(g, at::kFloat, 1, dl, "grad");
+  head_t(dl, at::kFloat, B * K, dl, "dl");
+  head_t(w, at::kFloat, K * C, dl, "weight");
+  head_t(feat, at::kFloat, B * C, dl, "feat");
+  head_t(keep, at::kByte, B * C, dl, "keep");
+  TORCH_CHECK(segs >= 0 && segs <= HW, "enas_head_bwd: 0 <= segs <= H * W");
+  Tensor dx, dw, db;
+  if (need_dx) dx = at::empty({B, H, W, C}, dl.options().dtype(at::kBFloat16));
+  if (need_dw) dw = at::empty({K, C}, dl.options());
+  if (need_db) db = at::empty({K}, dl.options());
+  EH::Bwd a{};
+  a.g = g.data_ptr<float>();
+  a.dl = dl.data_ptr<float>();
+  a.w = w.data_ptr<float>();
+  a.feat = feat.data_ptr<float>();
+  a.keep = keep.data_ptr<uint8_t>();
+  a.dx = need_dx ? dx.data_ptr() : nullptr;
+  a.dw = need_dw ? dw.data_ptr<float>() : nullptr;
+  a.db = need_db ? db.data_ptr<float>() : nullptr;
+  a.B = (int)B, a.HW = (int)HW, a.C = (int)C, a.K = (int)K;
+  a.mscale = (float)scale / (float)HW;
+  a.S = segs > 0 ? (int)segs : EH::segments((int)B, (int)HW, (int)C);
+  TORCH_CHECK(EH::launch_bwd(a, stream()) == hipSuccess, "enas_head_bwd launch failed");
+  return {dx, dw, db};
+}
+
 }  // namespace
 
 void register_dwconv(py::module& m) {
+  m.def("enas_head_fwd", &enas_head_fwd, "child head forward: pool, dropout, dense, softmax cross-entropy, sums");
+  m.def("enas_head_bwd", &enas_head_bwd, "its backward: dx, dW, db in one launch");
+  m.attr("ENAS_HEAD_MAX_K") = EH::kMaxK;
+  m.attr("ENAS_HEAD_MAX_C") = EH::kMaxC;
   m.def("enas_concat_fwd", &enas_concat_fwd, "ReLU + zero-pad + channel concat of NHWC bf16 sources");
   m.def("enas_concat_bwd", &enas_concat_bwd, "its backward: one gradient per source that wants one");
   m.attr("ENAS_CONCAT_MAX_SRC") = EC::kMaxSrc;

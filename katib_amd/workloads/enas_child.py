@@ -20,6 +20,8 @@ on the NHWC bf16 HIP kernels (``ops/batchnorm.py``, channel counts that are mult
 8), max / average pooling of the ``reduction`` op on the NHWC bf16 pool kernels
 (``ops/pool.py``), each layer's input - ReLU of the zero-pad concatenation of its sources -
 built by one kernel forward and one backward (``ops/enas_concat.py``; ``FUSED_INPUT``),
+with ``--head hip`` the head - pooling, dropout, classifier, loss and accuracy - in two launches
+forward and one backward (``ops/enas_head.py``; the default ``module`` keeps the torch modules),
 synthetic CIFAR-10-shaped data in HBM, and data parallelism over the trial's GPUs
 (``WORLD_SIZE`` ranks, RCCL all-reduce of the flat gradient) in place of
 ``tf.distribute.MirroredStrategy``.
@@ -54,6 +56,7 @@ from ..ops import conv as hconv
 from ..ops import pool as hpool
 from ..ops import dwconv as hdw
 from ..ops import enas_concat as hcat
+from ..ops import enas_head as hhead
 from ..ops.augment import PLAIN, AugSpec, augment_gather, cifar_lut
 from .common import CapturedStep, Timer, device, global_avg_pool, pattern_images, report
 
@@ -175,10 +178,12 @@ class ChildNet(nn.Module):
             sizes.append(op.hw)
         self.inputs = [[l - 1] + [i for i in range(l - 1) if l > 1 and arch[l - 1][1:l + 1][i] == 1]
                        for l in range(1, self.num_layers + 1)]
+        self.out_chw = (chans[-1], sizes[-1], sizes[-1])  # of the last layer
         self.drop = nn.Dropout(0.4)
         self.fc = nn.Linear(chans[-1], int(nn_config["output_sizes"][-1]))
 
-    def forward(self, x):
+    def features(self, x):
+        """The last layer's activation, the input of the head."""
         layers = [x]
         for op, ins in zip(self.ops, self.inputs):
             srcs = [layers[i] for i in ins]
@@ -187,7 +192,10 @@ class ChildNet(nn.Module):
                 layers.append(op(hcat.relu_pad_concat(srcs, relu=not pool), relu_done=True))
             else:
                 layers.append(op(_concat(srcs)))
-        return self.fc(self.drop(global_avg_pool(layers[-1])))
+        return layers[-1]
+
+    def forward(self, x):
+        return self.fc(self.drop(global_avg_pool(self.features(x))))
 
 
 def _chw(sizes):
@@ -223,6 +231,9 @@ def parse_args(argv):
     p.add_argument("--augment", type=str, default="auto", choices=["auto", "0", "1"],
                    help="random horizontal flip + translation by up to 10 %% (bilinear, reflected borders) in the "
                         "training batch gather; auto = on with --data-dir")
+    p.add_argument("--head", type=str, default="module", choices=["module", "hip"],
+                   help="pooling, dropout, classifier and loss: module = torch modules, hip = the fused HIP "
+                        "head kernels (dropout mask from the trial's Philox contract, keyed by --seed and the rank)")
     return p.parse_args(argv)
 
 
@@ -234,7 +245,7 @@ class ChildTrainer:
     ``index_select``."""
 
     def __init__(self, arch, nn_config, num_train=50000, num_valid=10000, batch_size=128, capture=True, seed=0,
-                 comm=None, data_dir="", augment=False):
+                 comm=None, data_dir="", augment=False, head="module"):
         from ..parallel.comm import Comm
 
         dev = device()
@@ -291,6 +302,24 @@ class ChildTrainer:
         self.idx = idx = torch.zeros(batch_size, dtype=torch.long, device=dev)
         self.acc_buf = acc_buf = torch.zeros(2, device=dev)  # loss sum, correct
         tx, ty = self.tx, self.ty
+        if head not in ("module", "hip"):
+            raise ValueError("head must be 'module' or 'hip', got %r" % (head,))
+        self.head = head
+        # the head kernels' step counter: read by the dropout draw, advanced by every training step
+        self.step_t = torch.zeros(1, dtype=torch.int32, device=dev)
+        if head == "hip" and cuda:
+            co, ho, wo = model.out_chw
+            why = hhead.limit(max(batch_size, 1000), ho, wo, co, model.fc.out_features)  # 1000: validate()'s chunk
+            if why:
+                raise ValueError("--head hip: " + why)
+
+        def hip_head_step(xb, yb):
+            with torch.autocast(device_type=dev.type, dtype=torch.bfloat16, enabled=cuda):
+                feats = model.features(xb)
+            drop = hhead.Drop(model.drop.p, comm.rank, seed, self.step_t)
+            loss = hhead.head_loss(feats, model.fc.weight, model.fc.bias, yb, drop, stats=acc_buf)
+            opt.zero_grad(set_to_none=False)
+            loss.backward()
 
         def train_step():
             if gather:  # flip + translate (or the plain, table-normalising gather) into the static buffer
@@ -298,13 +327,16 @@ class ChildTrainer:
             else:
                 xb = tx.index_select(0, idx)
             yb = ty.index_select(0, idx)
-            with torch.autocast(device_type=dev.type, dtype=torch.bfloat16, enabled=cuda):
-                logits = model(xb)
-            loss = F.cross_entropy(logits.float(), yb)
-            opt.zero_grad(set_to_none=False)
-            loss.backward()
-            acc_buf[0].add_(loss.detach())
-            acc_buf[1].add_((logits.argmax(1) == yb).sum())
+            if head == "hip":
+                hip_head_step(xb, yb)
+            else:
+                with torch.autocast(device_type=dev.type, dtype=torch.bfloat16, enabled=cuda):
+                    logits = model(xb)
+                loss = F.cross_entropy(logits.float(), yb)
+                opt.zero_grad(set_to_none=False)
+                loss.backward()
+                acc_buf[0].add_(loss.detach())
+                acc_buf[1].add_((logits.argmax(1) == yb).sum())
             if comm.world_size == 1:
                 opt.step()
             return acc_buf
@@ -345,6 +377,12 @@ class ChildTrainer:
                     yv = self.vy[i:i + vi.numel()]
                 else:
                     xv, yv = self.vx[i:i + chunk], self.vy[i:i + chunk]
+                if self.head == "hip":
+                    fc = self.model.fc
+                    ls, hits = hhead.head_eval(self.model.features(xv), fc.weight, fc.bias, yv)
+                    vl += float(ls)
+                    vc += float(hits)
+                    continue
                 lg = self.model(xv).float()
                 vl += float(F.cross_entropy(lg, yv, reduction="sum"))
                 vc += float((lg.argmax(1) == yv).sum())
@@ -359,7 +397,7 @@ def main(argv=None):
     print(">>> arch received by trial\n%s" % arch, flush=True)
     augment = bool(args.data_dir) if args.augment == "auto" else args.augment == "1"
     tr = ChildTrainer(arch, nn_config, args.num_train, args.num_valid, args.batch_size, bool(args.capture), args.seed,
-                      data_dir=args.data_dir, augment=augment)
+                      data_dir=args.data_dir, augment=augment, head=args.head)
     comm, dev, bs, steps = tr.comm, tr.dev, tr.bs, tr.steps
     gen = torch.Generator(device=dev).manual_seed(args.seed + comm.rank)
     timer = Timer()
