@@ -138,8 +138,8 @@ void concat_src(const Tensor& t, int64_t B, int64_t H, int64_t C, const char* na
               " must be [B, H, H, C] with a square map and the common batch size");
 }
 
-// xs[i] [B, H_i, H_i, C_i] -> out [B, m, m, sum C_i]
-void enas_concat_fwd(const std::vector<Tensor>& xs, const Tensor& out, bool relu) {
+// xs[i] [B, H_i, H_i, C_i] -> out [B, m, m, Cs]: Cs = sum C_i, with pad8 rounded up to a multiple of 8
+void enas_concat_fwd(const std::vector<Tensor>& xs, const Tensor& out, bool relu, bool pad8) {
   TORCH_CHECK(!xs.empty() && (int64_t)xs.size() <= EC::kMaxSrc, "enas_concat: 1 to ", EC::kMaxSrc, " sources, got ",
               xs.size());
   TORCH_CHECK(xs[0].dim() == 4, "enas_concat: sources are [B, H, H, C]");
@@ -154,16 +154,17 @@ void enas_concat_fwd(const std::vector<Tensor>& xs, const Tensor& out, bool relu
     tb.s[i].H = (int)xs[i].size(1);
     tb.s[i].C = (int)xs[i].size(3);
   }
-  TORCH_CHECK(EC::finish(tb, 0), "enas_concat: empty source or B * m * m * C >= 2^31");
-  concat_src(out, tb.B, tb.m, tb.Ct, "out");
+  TORCH_CHECK(EC::finish(tb, 0, pad8), "enas_concat: empty source or B * m * m * C >= 2^31");
+  concat_src(out, tb.B, tb.m, tb.Cs, "out");
   TORCH_CHECK(EC::launch_fwd(tb, relu, out.data_ptr(), stream()) == hipSuccess, "enas_concat_fwd launch failed");
 }
 
 // geom[i] = (H_i, C_i); xs[i] (read only with relu) and gxs[i] [B, H_i, H_i, C_i], gxs[i] None where no
-// gradient is wanted; gout [B, m, m, Ct] whose pixels lie gs >= Ct elements apart
+// gradient is wanted; gout [B, m, m, Cs] whose pixels lie gs >= Cs elements apart (Cs as in the forward;
+// channels >= Ct are never read into a gx)
 void enas_concat_bwd(const std::vector<std::vector<int64_t>>& geom, int64_t B,
                      const std::vector<c10::optional<Tensor>>& xs, const std::vector<c10::optional<Tensor>>& gxs,
-                     const Tensor& gout, bool relu) {
+                     const Tensor& gout, bool relu, bool pad8) {
   const size_t n = geom.size();
   TORCH_CHECK(n >= 1 && (int64_t)n <= EC::kMaxSrc, "enas_concat: 1 to ", EC::kMaxSrc, " sources, got ", n);
   TORCH_CHECK(xs.size() == n && gxs.size() == n && B >= 1 && B < (1ll << 31), "enas_concat_bwd: list lengths differ");
@@ -193,17 +194,17 @@ void enas_concat_bwd(const std::vector<std::vector<int64_t>>& geom, int64_t B,
   int64_t gs = 0;
   {
     EC::Table probe = tb;
-    TORCH_CHECK(EC::finish(probe, 0), "enas_concat: B * m * m * C >= 2^31");
+    TORCH_CHECK(EC::finish(probe, 0, pad8), "enas_concat: B * m * m * C >= 2^31");
     const int64_t m = probe.m;
-    TORCH_CHECK(gout.size(0) == B && gout.size(1) == m && gout.size(2) == m && gout.size(3) == probe.Ct,
-                "gout must be [B, m, m, Ct]");
-    gs = m > 1 ? gout.stride(2) : (B > 1 ? gout.stride(0) : probe.Ct);
-    TORCH_CHECK(gs >= probe.Ct && (m == 1 || gout.stride(1) == m * gs) && (B == 1 || gout.stride(0) == m * m * gs),
-                "gout must be dense up to a pixel stride >= Ct");
-    const int64_t last = (B * m * m - 1) * gs + probe.Ct;  // one past the last element read
+    TORCH_CHECK(gout.size(0) == B && gout.size(1) == m && gout.size(2) == m && gout.size(3) == probe.Cs,
+                "gout must be [B, m, m, Cs]");
+    gs = m > 1 ? gout.stride(2) : (B > 1 ? gout.stride(0) : probe.Cs);
+    TORCH_CHECK(gs >= probe.Cs && (m == 1 || gout.stride(1) == m * gs) && (B == 1 || gout.stride(0) == m * m * gs),
+                "gout must be dense up to a pixel stride >= Cs");
+    const int64_t last = (B * m * m - 1) * gs + probe.Cs;  // one past the last element read
     TORCH_CHECK((gout.storage_offset() + last) * 2 <= (int64_t)gout.storage().nbytes(), "gout reaches past its storage");
   }
-  TORCH_CHECK(EC::finish(tb, gs), "enas_concat: B * m * m * gs >= 2^31");
+  TORCH_CHECK(EC::finish(tb, gs, pad8), "enas_concat: B * m * m * gs >= 2^31");
   TORCH_CHECK(EC::launch_bwd(tb, relu, gout.data_ptr(), (int)gs, stream()) == hipSuccess, "enas_concat_bwd launch failed");
 }
 

@@ -4,7 +4,9 @@ Activations are bf16 NHWC (``torch.channels_last``), weights are the fp32 master
 parameters ([K, C, R, S]); the forward casts them to a bf16 [K][R][S][C] matrix, the
 backward returns an fp32 weight gradient (accumulated by the kernel in fp32) and a bf16
 input gradient. Channel counts that are not a multiple of 8 (the 3-channel image stem)
-are zero-padded to 8 on the fly.
+are zero-padded to 8 on the fly; an input that already carries the weight's input channels
+rounded up to a multiple of 8 (``enas_concat.relu_pad_concat(..., pad8=True)``) is taken as it is
+and gets its gradient over all of its channels.
 
 Used by the ResNet-18 trial (reference BASELINE config 3; the reference's own trial
 images delegate convolutions to cuDNN, e.g. ``examples/v1beta1/trial-images/
@@ -56,7 +58,9 @@ class _ConvFn(torch.autograd.Function):
     def forward(ctx, x, w, stride, padding, dilation, out_hw):
         k = kernels()
         N, C, H, W = x.shape
-        K, _, R, S = w.shape
+        K, Cw, R, S = w.shape
+        if C != Cw and C != (Cw + 7) // 8 * 8:
+            raise ValueError("conv2d: input has %d channels, the weight %d (or that rounded up to 8)" % (C, Cw))
         sh, sw = stride
         ph, pw = padding
         dh, dw = dilation
@@ -72,7 +76,7 @@ class _ConvFn(torch.autograd.Function):
         geom = [N, H, W, C8, K, R, S, OH, OW, sh, sw, ph, pw, dh, dw]
         k.conv_fwd(xn, wk, y, geom)
         ctx.save_for_backward(xn, wk)
-        ctx.geom, ctx.C, ctx.wdtype = geom, C, w.dtype
+        ctx.geom, ctx.C, ctx.Cw, ctx.wdtype = geom, C, Cw, w.dtype
         return y.permute(0, 3, 1, 2)  # NCHW view with channels_last memory
 
     @staticmethod
@@ -88,11 +92,11 @@ class _ConvFn(torch.autograd.Function):
             wt = wk.permute(3, 1, 2, 0).contiguous()  # [C8][R][S][K]
             dx = torch.empty((N, H, W, C8), device=gy.device, dtype=torch.bfloat16)
             k.conv_dgrad(gyn, wt, dx, ctx.geom)
-            gx = dx[..., :ctx.C].permute(0, 3, 1, 2)
+            gx = (dx if ctx.C == C8 else dx[..., :ctx.C]).permute(0, 3, 1, 2)
         if ctx.needs_input_grad[1]:
             dw32 = torch.zeros((K, R * S * C8), device=gy.device, dtype=torch.float32)
             k.conv_wgrad(xn, gyn, dw32, ctx.geom)
-            gw = dw32.view(K, R, S, C8)[..., :ctx.C].permute(0, 3, 1, 2).to(ctx.wdtype)
+            gw = dw32.view(K, R, S, C8)[..., :ctx.Cw].permute(0, 3, 1, 2).to(ctx.wdtype)
         return gx, gw, None, None, None, None
 
 

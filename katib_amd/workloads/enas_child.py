@@ -19,7 +19,9 @@ image input is zero-padded to 8 channels there, so no op falls back to MIOpen), 
 on the NHWC bf16 HIP kernels (``ops/batchnorm.py``, channel counts that are multiples of
 8), max / average pooling of the ``reduction`` op on the NHWC bf16 pool kernels
 (``ops/pool.py``), each layer's input - ReLU of the zero-pad concatenation of its sources -
-built by one kernel forward and one backward (``ops/enas_concat.py``; ``FUSED_INPUT``),
+built by one kernel forward and one backward (``ops/enas_concat.py``; ``FUSED_INPUT``; with
+``PAD8_INPUT`` a ``convolution`` layer whose channel sum is odd - the image as a skip source - gets
+that input already padded to the multiple of 8 its convolution reads, on the shifted 16-byte kernels),
 with ``--head hip`` the head - pooling, dropout, classifier, loss and accuracy - in two launches
 forward and one backward (``ops/enas_head.py``; the default ``module`` keeps the torch modules),
 synthetic CIFAR-10-shaped data in HBM, and data parallelism over the trial's GPUs
@@ -66,6 +68,13 @@ from .common import CapturedStep, Timer, device, global_avg_pool, pattern_images
 # Off until the captured step has been timed against the unfused one (ARCHITECTURE section 4,
 # profiles/enas_concat.log).
 FUSED_INPUT = False
+# On (with FUSED_INPUT): a `convolution` layer whose channel sum is no multiple of 8 (the 3-channel
+# image as a skip source: 67, 131, ...) gets its input from the fused kernels already padded to the
+# next multiple of 8 (`pad8`), which is what the implicit-GEMM convolution reads: no F.pad copy of the
+# layer's largest tensor, no slice of its gradient, and the shifted 16-byte kernels in place of the
+# element ones. Same values and gradients. Off under the same rule as FUSED_INPUT
+# (profiles/enas_concat_shift.log has the op alone).
+PAD8_INPUT = False
 
 
 def _same_pad(size: int, k: int, s: int):
@@ -188,7 +197,10 @@ class ChildNet(nn.Module):
         for op, ins in zip(self.ops, self.inputs):
             srcs = [layers[i] for i in ins]
             pool = op.kind == "reduction"
-            if FUSED_INPUT and not (pool and len(srcs) == 1) and hcat.supported(srcs):
+            if (FUSED_INPUT and PAD8_INPUT and op.kind == "convolution" and len(srcs) > 1
+                    and sum(s.shape[1] for s in srcs) % 8 and hcat.supported(srcs, pad8=True)):
+                layers.append(op(hcat.relu_pad_concat(srcs, relu=True, pad8=True), relu_done=True))
+            elif FUSED_INPUT and not (pool and len(srcs) == 1) and hcat.supported(srcs):
                 layers.append(op(hcat.relu_pad_concat(srcs, relu=not pool), relu_done=True))
             else:
                 layers.append(op(_concat(srcs)))
