@@ -1,9 +1,13 @@
-// torch bindings for the ENAS controller kernel (module katib_amd._hipkern, enas_* entry points).
-// Shapes, dtypes, devices and the LDS budget are validated here before the launch.
+// torch bindings for the ENAS controller kernel and the child's one-launch Adam (module
+// katib_amd._hipkern, enas_* entry points). Shapes, dtypes, devices and the LDS budget are validated
+// here before the launch.
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
+#include <cstring>
+
 #include "enas_ctrl.h"
+#include "enas_optim.h"
 
 using at::Tensor;
 namespace E = katib_hip::enas;
@@ -123,9 +127,99 @@ void enas_train(Tensor P, Tensor M, Tensor V, Tensor G, Tensor tape, Tensor arcs
   E::launch(a, 1, c10::hip::getCurrentHIPStream().stream());
 }
 
+// ---- the child's optimizer (enas_optim.hip)
+namespace EO = katib_hip::enasoptim;
+
+void adam_t(const Tensor& t, at::ScalarType ty, int64_t n, const char* name, const Tensor& ref) {
+  TORCH_CHECK(t.is_cuda() && t.device() == ref.device() && t.scalar_type() == ty && t.is_contiguous() && t.numel() == n,
+              "enas_adam: ", name, " must be a contiguous tensor of ", n, " elements on the parameters' GPU");
+}
+
+// One entry per parameter tensor: (kind, p, g, m, v, img or None, wt or None, K, C, RS, rows) with kind
+// 0 = flat, 1 = conv, 2 = depthwise (enas_optim.h). Returns (device table as a uint8 tensor, segment
+// count, total workgroups).
+py::tuple adam_table(const std::vector<py::tuple>& entries) {
+  TORCH_CHECK(!entries.empty(), "enas_adam_table: no parameters");
+  std::vector<EO::Seg> segs;
+  int64_t tiles = 0;
+  const Tensor first = entries[0][1].cast<Tensor>();
+  for (const auto& e : entries) {
+    TORCH_CHECK(e.size() == 11, "enas_adam_table: entries are (kind, p, g, m, v, img, wt, K, C, RS, rows)");
+    const int64_t kind = e[0].cast<int64_t>(), K = e[7].cast<int64_t>(), C = e[8].cast<int64_t>(),
+                  RS = e[9].cast<int64_t>(), rows = e[10].cast<int64_t>();
+    const Tensor p = e[1].cast<Tensor>(), g = e[2].cast<Tensor>(), m = e[3].cast<Tensor>(), v = e[4].cast<Tensor>();
+    const int64_t n = p.numel();
+    TORCH_CHECK(n >= 1 && n < (1ll << 31), "enas_adam_table: a parameter has 1 to 2^31 - 1 elements");
+    adam_t(p, at::kFloat, n, "p", first);
+    adam_t(m, at::kFloat, n, "m", first);
+    adam_t(v, at::kFloat, n, "v", first);
+    EO::Seg s{};
+    s.kind = (int)kind;
+    s.n = (int)n;
+    if (kind == EO::kFlat) {
+      TORCH_CHECK(e[5].is_none() && e[6].is_none(), "enas_adam_table: a flat segment has no image");
+      adam_t(g, at::kFloat, n, "g", first);
+    } else if (kind == EO::kConv) {
+      const int64_t C8 = (C + 7) / 8 * 8;
+      TORCH_CHECK(K >= 1 && C >= 1 && RS >= 1 && n == K * RS * C, "enas_adam_table: filter geometry does not match p");
+      TORCH_CHECK(K * RS * C8 < (1ll << 31), "enas_adam_table: K * RS * C8 >= 2^31");
+      TORCH_CHECK(!e[5].is_none(), "enas_adam_table: a conv segment needs its [K][RS][C8] image");
+      adam_t(g, at::kFloat, K * RS * C8, "g", first);
+      const Tensor wk = e[5].cast<Tensor>();
+      adam_t(wk, at::kBFloat16, K * RS * C8, "wk", first);
+      s.img = wk.data_ptr();
+      if (!e[6].is_none()) {
+        const Tensor wt = e[6].cast<Tensor>();
+        adam_t(wt, at::kBFloat16, K * RS * C8, "wt", first);
+        s.wt = wt.data_ptr();
+      }
+      s.K = (int)K, s.C = (int)C, s.C8 = (int)C8, s.RS = (int)RS;
+    } else {
+      TORCH_CHECK(kind == EO::kDepthwise, "enas_adam_table: kind is 0, 1 or 2");
+      TORCH_CHECK(K >= 1 && RS >= 1 && n == K * RS && rows >= 1 && rows <= EO::kMaxRows,
+                  "enas_adam_table: depthwise geometry does not match p, or rows outside [1, ", EO::kMaxRows, "]");
+      TORCH_CHECK(rows * n < (1ll << 31), "enas_adam_table: rows * Co * KK >= 2^31");
+      TORCH_CHECK(!e[5].is_none() && e[6].is_none(), "enas_adam_table: a depthwise segment has one image");
+      adam_t(g, at::kFloat, rows * n, "partials", first);
+      const Tensor img = e[5].cast<Tensor>();
+      adam_t(img, at::kFloat, n, "image", first);
+      s.img = img.data_ptr();
+      s.K = (int)K, s.RS = (int)RS, s.rows = (int)rows;
+    }
+    s.p = p.data_ptr<float>();
+    s.g = g.data_ptr<float>();
+    s.m = m.data_ptr<float>();
+    s.v = v.data_ptr<float>();
+    s.tile0 = (int)tiles;
+    tiles += EO::tiles(s);
+    TORCH_CHECK(tiles < (1ll << 31), "enas_adam_table: too many workgroups");
+    segs.push_back(s);
+  }
+  auto host = at::empty({(int64_t)(segs.size() * sizeof(EO::Seg))}, at::TensorOptions().dtype(at::kByte));
+  std::memcpy(host.data_ptr(), segs.data(), segs.size() * sizeof(EO::Seg));
+  return py::make_tuple(host.to(first.device()), (int64_t)segs.size(), tiles);
+}
+
+// counters: int32 [2] = (completed updates t, ticket word)
+void adam(const Tensor& table, int64_t nseg, int64_t tiles, const Tensor& counters, double lr, double beta1,
+          double beta2, double eps, bool update) {
+  TORCH_CHECK(table.is_cuda() && table.scalar_type() == at::kByte && table.is_contiguous() &&
+                  table.numel() == nseg * (int64_t)sizeof(EO::Seg) && nseg >= 1 && tiles >= 1 && tiles < (1ll << 31),
+              "enas_adam: table must come from enas_adam_table");
+  adam_t(counters, at::kInt, 2, "counters", table);
+  TORCH_CHECK(EO::launch(reinterpret_cast<const EO::Seg*>(table.data_ptr()), (int)nseg, (int)tiles,
+                         counters.data_ptr<int32_t>(), (float)lr, (float)beta1, (float)beta2, (float)eps,
+                         update ? 1 : 0, c10::hip::getCurrentHIPStream().stream()) == hipSuccess,
+              "enas_adam launch failed");
+}
+
 }  // namespace
 
 void register_enas(py::module& m) {
+  m.def("enas_adam_table", &adam_table, "validate + upload the segment table of the child's one-launch Adam");
+  m.def("enas_adam", &adam,
+        "one-launch Adam over every segment: zeroes the gradient buffers, sums the depthwise partials, re-emits "
+        "the weight images and advances the device step counter (update=False: images only)");
   m.def("enas_sample", &enas_sample, "ENAS controller: sample one arc per workgroup");
   m.def("enas_train", &enas_train, "ENAS controller: nsteps REINFORCE steps (sample, BPTT, Adam) in one workgroup",
         py::arg("P"), py::arg("M"), py::arg("V"), py::arg("G"), py::arg("tape"), py::arg("arcs"), py::arg("logs"),

@@ -100,6 +100,56 @@ class _ConvFn(torch.autograd.Function):
         return gx, gw, None, None, None, None
 
 
+class _ConvPreparedFn(torch.autograd.Function):
+    """:class:`_ConvFn` over the buffers of ``ops.enas_optim.ChildAdam``: ``prep.wk`` / ``prep.wt`` are the
+    bf16 ``[K][R][S][C8]`` / ``[C8][R][S][K]`` images the optimizer's launch writes and ``prep.g`` the fp32
+    accumulator ``[K][R*S*C8]`` it reads and zeroes, so neither pass copies a weight, fills an accumulator
+    or permutes a gradient. ``w``, the master parameter, only anchors the node in autograd (the backward
+    runs when ``x`` wants no gradient, too); its ``.grad`` stays None."""
+
+    @staticmethod
+    def forward(ctx, x, w, prep, stride, padding, dilation, out_hw):
+        k = kernels()
+        N, C, H, W = x.shape
+        K, Cw, R, S = w.shape
+        C8 = (Cw + 7) // 8 * 8
+        if C != Cw and C != C8:
+            raise ValueError("conv2d: input has %d channels, the weight %d (or that rounded up to 8)" % (C, Cw))
+        sh, sw = stride
+        ph, pw = padding
+        dh, dw = dilation
+        if out_hw is None:
+            OH = (H + 2 * ph - dh * (R - 1) - 1) // sh + 1
+            OW = (W + 2 * pw - dw * (S - 1) - 1) // sw + 1
+        else:
+            OH, OW = out_hw
+        xn = _pad_c(_nhwc(x.to(torch.bfloat16)), C8)
+        y = torch.empty((N, OH, OW, K), device=x.device, dtype=torch.bfloat16)
+        geom = [N, H, W, C8, K, R, S, OH, OW, sh, sw, ph, pw, dh, dw]
+        k.conv_fwd(xn, prep.wk, y, geom)
+        ctx.save_for_backward(xn)
+        ctx.geom, ctx.C, ctx.prep = geom, C, prep
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, gy):
+        k = kernels()
+        xn, = ctx.saved_tensors
+        prep = ctx.prep
+        N, H, W, C8, K = ctx.geom[:5]
+        gyn = _nhwc(gy.to(torch.bfloat16))
+        gx = None
+        if ctx.needs_input_grad[0]:
+            if prep.wt is None:
+                raise RuntimeError("prepared conv: the input wants a gradient, the optimizer holds no [C8][R][S][K] "
+                                   "image for this layer")
+            dx = torch.empty((N, H, W, C8), device=gy.device, dtype=torch.bfloat16)
+            k.conv_dgrad(gyn, prep.wt, dx, ctx.geom)
+            gx = (dx if ctx.C == C8 else dx[..., :ctx.C]).permute(0, 3, 1, 2)
+        k.conv_wgrad(xn, gyn, prep.g.view(K, -1), ctx.geom)
+        return gx, None, None, None, None, None, None
+
+
 def channel_sum_nhwc(g: torch.Tensor) -> torch.Tensor:
     """Sum of an [N, C, H, W] gradient over (N, H, W) -> fp32 [C] on the HIP channel-sum kernel
     (C % 8 == 0), never through PyTorch's cross-workgroup reduction: on this ROCm stack that
@@ -134,12 +184,16 @@ def bias_add(y: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
 
 
 def conv2d(x: torch.Tensor, w: torch.Tensor, bias=None, stride=1, padding=0, dilation=1,
-           out_hw=None) -> torch.Tensor:
+           out_hw=None, prep=None) -> torch.Tensor:
     """bf16 NHWC implicit-GEMM convolution (groups=1) with an fp32 weight master.
-    ``out_hw`` overrides the output size for asymmetric padding (``padding`` = top/left)."""
+    ``out_hw`` overrides the output size for asymmetric padding (``padding`` = top/left). ``prep``: the
+    record ``ops.enas_optim.ChildAdam`` attached to the layer (:class:`_ConvPreparedFn`)."""
     if x.dtype != torch.bfloat16:
         x = x.to(torch.bfloat16)  # like autocast; keeps the Function's input grad bf16
-    y = _ConvFn.apply(x, w, _pair(stride), _pair(padding), _pair(dilation), out_hw)
+    if prep is not None:
+        y = _ConvPreparedFn.apply(x, w, prep, _pair(stride), _pair(padding), _pair(dilation), out_hw)
+    else:
+        y = _ConvFn.apply(x, w, _pair(stride), _pair(padding), _pair(dilation), out_hw)
     if bias is not None:
         y = bias_add(y, bias)
     return y
@@ -149,7 +203,7 @@ def supported(x: torch.Tensor, w: torch.Tensor, groups: int = 1) -> bool:
     return x.is_cuda and groups == 1 and w.shape[0] % 8 == 0 and x.dim() == 4
 
 
-def same_conv2d(x, w, bias, stride: int):
+def same_conv2d(x, w, bias, stride: int, prep=None):
     """TF/Keras ``padding='same'`` (bottom/right-heavy when the total padding is odd)."""
     k = w.shape[2]
     outs, tops = [], []
@@ -158,7 +212,7 @@ def same_conv2d(x, w, bias, stride: int):
         total = max((out - 1) * stride + k - size, 0)
         outs.append(out)
         tops.append(total // 2)
-    return conv2d(x, w, bias, stride, tuple(tops), 1, tuple(outs))
+    return conv2d(x, w, bias, stride, tuple(tops), 1, tuple(outs), prep)
 
 
 class Conv2d(nn.Conv2d):
@@ -167,5 +221,6 @@ class Conv2d(nn.Conv2d):
     def forward(self, x):
         if (supported(x, self.weight, self.groups) and self.padding_mode == "zeros"
                 and isinstance(self.padding, tuple)):
-            return conv2d(x, self.weight, self.bias, self.stride, self.padding, self.dilation)
+            return conv2d(x, self.weight, self.bias, self.stride, self.padding, self.dilation,
+                          prep=getattr(self, "prep", None))
         return super().forward(x)

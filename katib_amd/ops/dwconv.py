@@ -75,11 +75,55 @@ class _DwFn(torch.autograd.Function):
         return gx, gw, gb, None
 
 
-def depthwise_same(x: torch.Tensor, weight: torch.Tensor, bias, stride: int) -> torch.Tensor:
-    """Keras ``padding='same'`` depthwise convolution (bf16 NHWC in / out)."""
+class _DwPreparedFn(torch.autograd.Function):
+    """:class:`_DwFn` over the buffers of ``ops.enas_optim.ChildAdam``: ``prep.img`` is the fp32 tap-major
+    ``[K*K][Co]`` image the optimizer's launch writes, and the backward leaves the per-workgroup partials
+    in ``prep.partials(rows)`` for that launch to sum - no weight copy, no ``sum(0)``. ``w``, the master
+    parameter, only anchors the node in autograd; its ``.grad`` stays None."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, prep, stride):
+        k = kernels()
+        N, C, H, W = x.shape
+        Co, _, K, _ = w.shape
+        dm = Co // C
+        pt, OH = _same(H, K, stride)
+        pl, OW = _same(W, K, stride)
+        geom = [N, H, W, C, dm, K, stride, pt, pl, OH, OW]
+        xn = x.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()
+        y = torch.empty((N, OH, OW, Co), device=x.device, dtype=torch.bfloat16)
+        k.dw_fwd(xn, prep.img, b.detach().float().contiguous() if b is not None else None, y, geom)
+        ctx.save_for_backward(xn)
+        ctx.geom, ctx.prep, ctx.has_b = geom, prep, b is not None
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, gy):
+        k = kernels()
+        xn, = ctx.saved_tensors
+        prep = ctx.prep
+        N, H, W, C, dm = ctx.geom[:5]
+        gyn = gy.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()
+        gx = gb = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty((N, H, W, C), device=gy.device, dtype=torch.bfloat16)
+            k.dw_dgrad(gyn, prep.img, dx, ctx.geom)
+            gx = dx.permute(0, 3, 1, 2)
+        k.dw_wgrad(xn, gyn, prep.partials(k.dw_wgrad_rows(ctx.geom)), ctx.geom)
+        if ctx.has_b and ctx.needs_input_grad[2]:
+            gb = torch.empty(C * dm, device=gy.device, dtype=torch.float32)
+            k.channel_sum(gyn.view(-1, C * dm), gb)
+        return gx, None, gb, None, None
+
+
+def depthwise_same(x: torch.Tensor, weight: torch.Tensor, bias, stride: int, prep=None) -> torch.Tensor:
+    """Keras ``padding='same'`` depthwise convolution (bf16 NHWC in / out). ``prep``: the record
+    ``ops.enas_optim.ChildAdam`` attached to the layer (:class:`_DwPreparedFn`; ``C % 8 == 0``)."""
     if x.dtype != torch.bfloat16:
         x = x.to(torch.bfloat16)
     C = x.shape[1]
+    if prep is not None:
+        return _DwPreparedFn.apply(x, weight, bias, prep, int(stride))
     if C % 8 == 0:
         return _DwFn.apply(x, weight, bias, int(stride))
     # zero channels C..C8-1: output channel o = c*DM + j, so the real outputs are the first C*DM

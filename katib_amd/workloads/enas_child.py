@@ -24,6 +24,11 @@ built by one kernel forward and one backward (``ops/enas_concat.py``; ``FUSED_IN
 that input already padded to the multiple of 8 its convolution reads, on the shifted 16-byte kernels),
 with ``--head hip`` the head - pooling, dropout, classifier, loss and accuracy - in two launches
 forward and one backward (``ops/enas_head.py``; the default ``module`` keeps the torch modules),
+with ``--optim hip`` Adam, the zeroing of the gradients, the sum of the depthwise partial gradients and
+the bf16 / tap-major weight images of the convolutions in one launch per step (``ops/enas_optim.py``:
+the convolutions then read the optimizer's images and write their weight gradients into its buffers,
+with no weight copy, accumulator fill or gradient permute of their own; one GPU only; the default
+``module`` keeps ``torch.optim.Adam``),
 synthetic CIFAR-10-shaped data in HBM, and data parallelism over the trial's GPUs
 (``WORLD_SIZE`` ranks, RCCL all-reduce of the flat gradient) in place of
 ``tf.distribute.MirroredStrategy``.
@@ -93,10 +98,11 @@ class _SameConv(nn.Module):
 
     def forward(self, x):
         c = self.conv
+        prep = getattr(self, "prep", None)  # attached by ops.enas_optim.ChildAdam: its images and buffers
         if hconv.supported(x, c.weight, c.groups):  # HIP implicit-GEMM (MFMA) path
-            return hconv.same_conv2d(x, c.weight, c.bias, self.s)
+            return hconv.same_conv2d(x, c.weight, c.bias, self.s, prep)
         if c.groups > 1 and hdw.supported(x, c.weight, c.groups, self.s):  # HIP depthwise (NHWC) path
-            return hdw.depthwise_same(x, c.weight, c.bias, self.s)
+            return hdw.depthwise_same(x, c.weight, c.bias, self.s, prep)
         t, b, _ = _same_pad(x.shape[2], self.k, self.s)
         l, r, _ = _same_pad(x.shape[3], self.k, self.s)
         return self.conv(F.pad(x, (l, r, t, b)))
@@ -246,6 +252,9 @@ def parse_args(argv):
     p.add_argument("--head", type=str, default="module", choices=["module", "hip"],
                    help="pooling, dropout, classifier and loss: module = torch modules, hip = the fused HIP "
                         "head kernels (dropout mask from the trial's Philox contract, keyed by --seed and the rank)")
+    p.add_argument("--optim", type=str, default="module", choices=["module", "hip"],
+                   help="module = torch.optim.Adam, hip = Adam, gradient zeroing and the convolutions' weight "
+                        "images in one HIP launch per step (one GPU)")
     return p.parse_args(argv)
 
 
@@ -257,13 +266,19 @@ class ChildTrainer:
     ``index_select``."""
 
     def __init__(self, arch, nn_config, num_train=50000, num_valid=10000, batch_size=128, capture=True, seed=0,
-                 comm=None, data_dir="", augment=False, head="module"):
+                 comm=None, data_dir="", augment=False, head="module", optim="module"):
         from ..parallel.comm import Comm
 
         dev = device()
         cuda = dev.type == "cuda"
         torch.manual_seed(seed)
         self.comm = comm or (Comm.from_env(dev.type) if cuda else Comm())
+        if optim not in ("module", "hip"):
+            raise ValueError("optim must be 'module' or 'hip', got %r" % (optim,))
+        if optim == "hip" and not (cuda and self.comm.world_size == 1):
+            raise ValueError("--optim hip needs a GPU and world_size == 1 (the gradient all-reduce does not reach "
+                             "the optimizer's buffers); got device %s, world_size %d" % (dev.type, self.comm.world_size))
+        self.optim = optim
         self.dev, self.cuda = dev, cuda
         mf = torch.channels_last if cuda else torch.contiguous_format
         c, h, w = _chw(nn_config["input_sizes"])
@@ -304,10 +319,15 @@ class ChildTrainer:
             flat0 = torch.nn.utils.parameters_to_vector(model.parameters()).detach()
             comm.broadcast_(flat0)
             torch.nn.utils.vector_to_parameters(flat0, model.parameters())
-        self.opt = opt = torch.optim.Adam(model.parameters(), lr=1e-3, fused=cuda, capturable=cuda)
         self.params = list(model.parameters())
-        for p_ in self.params:
-            p_.grad = torch.zeros_like(p_)
+        if optim == "hip":  # owns the masters, the gradient buffers and the weight images
+            from ..ops.enas_optim import ChildAdam
+
+            self.opt = opt = ChildAdam(model, lr=1e-3)
+        else:
+            self.opt = opt = torch.optim.Adam(model.parameters(), lr=1e-3, fused=cuda, capturable=cuda)
+            for p_ in self.params:
+                p_.grad = torch.zeros_like(p_)
         self.bs = batch_size
         self.shard = num_train // comm.world_size
         self.steps = max(1, self.shard // batch_size)
@@ -330,7 +350,8 @@ class ChildTrainer:
                 feats = model.features(xb)
             drop = hhead.Drop(model.drop.p, comm.rank, seed, self.step_t)
             loss = hhead.head_loss(feats, model.fc.weight, model.fc.bias, yb, drop, stats=acc_buf)
-            opt.zero_grad(set_to_none=False)
+            if optim != "hip":  # ChildAdam's launch has zeroed them
+                opt.zero_grad(set_to_none=False)
             loss.backward()
 
         def train_step():
@@ -345,7 +366,8 @@ class ChildTrainer:
                 with torch.autocast(device_type=dev.type, dtype=torch.bfloat16, enabled=cuda):
                     logits = model(xb)
                 loss = F.cross_entropy(logits.float(), yb)
-                opt.zero_grad(set_to_none=False)
+                if optim != "hip":
+                    opt.zero_grad(set_to_none=False)
                 loss.backward()
                 acc_buf[0].add_(loss.detach())
                 acc_buf[1].add_((logits.argmax(1) == yb).sum())
@@ -409,7 +431,7 @@ def main(argv=None):
     print(">>> arch received by trial\n%s" % arch, flush=True)
     augment = bool(args.data_dir) if args.augment == "auto" else args.augment == "1"
     tr = ChildTrainer(arch, nn_config, args.num_train, args.num_valid, args.batch_size, bool(args.capture), args.seed,
-                      data_dir=args.data_dir, augment=augment, head=args.head)
+                      data_dir=args.data_dir, augment=augment, head=args.head, optim=args.optim)
     comm, dev, bs, steps = tr.comm, tr.dev, tr.bs, tr.steps
     gen = torch.Generator(device=dev).manual_seed(args.seed + comm.rank)
     timer = Timer()
