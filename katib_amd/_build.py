@@ -109,7 +109,8 @@ _VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
 # (48 / 50, 44 / 24, 14 / 9 VGPRs, no scratch). The host pass does not know the feature and says so.
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_TU_FLAGS = {"transformer.hip": _VGPR_FORM, "darts_ops_fwd.hip": _VGPR_FORM, "darts_ops_pwb.hip": _VGPR_FORM,
-                "enas_concat.hip": _NO_PK_F32, "enas_head.hip": _NO_PK_F32, "enas_optim.hip": _NO_PK_F32}
+                "enas_concat.hip": _NO_PK_F32, "enas_head.hip": _NO_PK_F32, "enas_optim.hip": _NO_PK_F32,
+                "enas_sepconv.hip": _NO_PK_F32}
 
 
 def hip_target() -> str:

@@ -1,0 +1,162 @@
+"""Separable convolution of the ENAS child in one HIP kernel per direction (``csrc/hip/enas_sepconv.hip``).
+
+``separable_convolution`` (reference ``op_library.py:22-155``: Keras ``SeparableConv2D``, ``padding='same'``)
+is a depthwise convolution followed by a 1x1 convolution with a bias. On the split path those are
+``dw_fwd`` and the 1x1 implicit GEMM with the depthwise result ``d`` ``[N, OH, OW, C*dm]`` bf16 between them
+in HBM, kept for the backward. :func:`separable_same` keeps ``d`` on the chip: the forward is one launch
+(depthwise on the VALU into an LDS tile, pointwise on MFMA, bias on the accumulator), the backward one
+launch that recomputes ``d`` with the forward's device function and forms ``gd = gy . wp`` and the
+pointwise weight gradient, then the existing ``dw_dgrad`` / ``dw_wgrad`` on ``gd`` and ``channel_sum`` for the
+bias. Only ``x`` is saved.
+
+Rounding points: ``d = bf16(fp32 tap sum)``, ``y = bf16(fp32 sum + bias)``, ``gd = bf16(fp32 sum)``; the
+pointwise weights are read as bf16, as the implicit GEMM reads them; the pointwise weight gradient is fp32
+(atomic adds: not bit-reproducible), everything else is deterministic.
+
+Served: K in {3, 5, 7}, stride in {1, 2}, dm in {1, 2}, ``C % 8 == 0``, ``F % 16 == 0`` and ``F <= 128``,
+``N*H*W*max(C*dm, F) < 2^31``, and a map the kernels can cut into bands (at most 128 output columns, one
+output row's input patch within the LDS: ``sep_plan``). Anything else stays on the split path.
+"""
+
+from __future__ import annotations
+
+import torch
+import torch.nn.functional as F_
+
+from .conv import kernels
+from .dwconv import _same
+
+
+def _geom(x, dw_weight, pw_weight, stride):
+    N, C, H, W = x.shape
+    Cd, _, K, _ = dw_weight.shape
+    pt, OH = _same(H, K, stride)
+    pl, OW = _same(W, K, stride)
+    return [N, H, W, C, Cd // C, K, int(stride), pt, pl, OH, OW, pw_weight.shape[0]]
+
+
+def supported(x: torch.Tensor, dw_weight: torch.Tensor, pw_weight: torch.Tensor, stride: int) -> bool:
+    if not (x.is_cuda and x.dim() == 4 and dw_weight.dim() == 4 and pw_weight.dim() == 4):
+        return False
+    N, C, H, W = x.shape
+    Cd, one, K, K2 = dw_weight.shape
+    Fo = pw_weight.shape[0]
+    if not (C > 0 and C % 8 == 0 and Cd in (C, 2 * C) and one == 1 and K == K2 and K in (3, 5, 7)
+            and stride in (1, 2) and tuple(pw_weight.shape[1:]) == (Cd, 1, 1) and Fo % 16 == 0 and 16 <= Fo <= 128
+            and N * H * W * max(Cd, Fo) < 2 ** 31):
+        return False
+    return kernels().sep_plan(_geom(x, dw_weight, pw_weight, stride)) is not None
+
+
+class _SepFn(torch.autograd.Function):
+    """Without ``prep`` records the weight images are built here, as ``_DwFn`` / ``_ConvFn`` build them, and
+    the backward returns both weight gradients. With the ``ChildAdam`` records it reads ``prep_dw.img``,
+    ``prep_pw.wk`` / ``prep_pw.wt`` and writes into ``prep_pw.g`` and ``prep_dw.partials(rows)``; the masters
+    only anchor the node, as in ``_ConvPreparedFn``, and their ``.grad`` stays None."""
+
+    @staticmethod
+    def forward(ctx, x, wd, wp, b, stride, prep_dw, prep_pw):
+        k = kernels()
+        geom = _geom(x, wd, wp, stride)
+        N, H, W, C, dm, K, S, pt, pl, OH, OW, Fo = geom
+        Cd = C * dm
+        xn = x.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()
+        if prep_dw is None:
+            img = wd.detach().float().reshape(Cd, K * K).t().contiguous()  # [K*K][Cd] tap-major
+            wk = wp.detach().reshape(Fo, Cd).to(torch.bfloat16).contiguous()  # [F][Cd]
+            ctx.save_for_backward(xn, img, wk)
+        else:
+            img, wk = prep_dw.img, prep_pw.wk
+            ctx.save_for_backward(xn)
+        y = torch.empty((N, OH, OW, Fo), device=x.device, dtype=torch.bfloat16)
+        k.sep_fwd(xn, img, wk, b.detach().float().contiguous() if b is not None else None, y, geom)
+        ctx.geom, ctx.prep = geom, (prep_dw, prep_pw)
+        ctx.meta = (wd.shape, wd.dtype, wp.shape, wp.dtype, b is not None)
+        return y.permute(0, 3, 1, 2)  # NCHW view, channels_last memory
+
+    @staticmethod
+    def backward(ctx, gy):
+        k = kernels()
+        prep_dw, prep_pw = ctx.prep
+        N, H, W, C, dm, K, S, pt, pl, OH, OW, Fo = ctx.geom
+        Cd, dwgeom = C * dm, ctx.geom[:11]
+        wd_shape, wd_dtype, wp_shape, wp_dtype, has_b = ctx.meta
+        dev = gy.device
+        gyn = gy.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()
+        gx = gwd = gwp = gb = None
+        if prep_dw is None:
+            xn, img, wk = ctx.saved_tensors
+            wt = wk.t().contiguous()  # [Cd][F]
+            acc = torch.zeros((Fo, Cd), device=dev, dtype=torch.float32)
+        else:
+            xn, = ctx.saved_tensors
+            img, wt, acc = prep_dw.img, prep_pw.wt, prep_pw.g.view(Fo, Cd)
+            if wt is None:
+                raise RuntimeError("fused separable conv: the optimizer holds no [Cd][F] image for the pointwise layer")
+        gd = torch.empty((N, OH, OW, Cd), device=dev, dtype=torch.bfloat16)
+        k.sep_bwd_pw(xn, img, wt, gyn, gd, acc, ctx.geom)
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty((N, H, W, C), device=dev, dtype=torch.bfloat16)
+            k.dw_dgrad(gd, img, dx, dwgeom)
+            gx = dx.permute(0, 3, 1, 2)
+        rows = k.dw_wgrad_rows(dwgeom)
+        if prep_dw is not None:
+            k.dw_wgrad(xn, gd, prep_dw.partials(rows), dwgeom)
+        else:
+            if ctx.needs_input_grad[1]:
+                part = torch.empty((rows, Cd, K * K), device=dev, dtype=torch.float32)
+                k.dw_wgrad(xn, gd, part, dwgeom)
+                gwd = part.sum(0).view(wd_shape).to(wd_dtype)
+            if ctx.needs_input_grad[2]:
+                gwp = acc.view(wp_shape).to(wp_dtype)
+        if has_b and ctx.needs_input_grad[3]:  # HIP channel sum: no PyTorch reduction under capture
+            gb = torch.empty(Fo, device=dev, dtype=torch.float32)
+            k.channel_sum(gyn.view(-1, Fo), gb)
+        return gx, gwd, gwp, gb, None, None, None
+
+
+def separable_same(x, dw_weight, pw_weight, pw_bias, stride, prep_dw=None, prep_pw=None):
+    """Keras ``SeparableConv2D(padding='same')`` without its activation: bf16 channels-last in and out.
+    ``dw_weight`` ``[C*dm, 1, K, K]`` and ``pw_weight`` ``[F, C*dm, 1, 1]`` are the fp32 masters, ``pw_bias``
+    ``[F]`` or None; ``prep_dw`` / ``prep_pw``: the records ``ops.enas_optim.ChildAdam`` attached to the two
+    layers (both or neither)."""
+    if (prep_dw is None) != (prep_pw is None):
+        raise ValueError("fused separable conv: both layers' ChildAdam records or neither")
+    if not supported(x, dw_weight, pw_weight, stride):
+        raise ValueError("fused separable conv: not served (see ops.enas_sepconv.supported): x %s, dw %s, pw %s, "
+                         "stride %s" % (tuple(x.shape), tuple(dw_weight.shape), tuple(pw_weight.shape), stride))
+    if x.dtype != torch.bfloat16:
+        x = x.to(torch.bfloat16)
+    return _SepFn.apply(x, dw_weight, pw_weight, pw_bias, int(stride), prep_dw, prep_pw)
+
+
+class _RoundBf16(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, t):
+        return t.to(torch.bfloat16).to(t.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.to(torch.bfloat16).to(g.dtype)
+
+
+def round_bf16(t: torch.Tensor) -> torch.Tensor:
+    """The rounding hook of :func:`reference`: the value to bf16 forward, its gradient to bf16 backward."""
+    return _RoundBf16.apply(t)
+
+
+def reference(x, wd, wp, b, stride, dm, rounding=None):
+    """The same op in plain torch, in the dtype of its inputs: ``x`` ``[N, C, H, W]``, ``wd`` ``[C*dm, 1, K, K]``,
+    ``wp`` ``[F, C*dm, 1, 1]``, ``b`` ``[F]`` or None. ``rounding`` (:func:`round_bf16`) is applied to ``d`` -
+    whose gradient is ``gd`` - and to ``y``: the kernels' rounding points."""
+    K = wd.shape[-1]
+    pt, OH = _same(x.shape[2], K, stride)
+    pl, OW = _same(x.shape[3], K, stride)
+    pb = max((OH - 1) * stride + K - x.shape[2], 0) - pt
+    pr = max((OW - 1) * stride + K - x.shape[3], 0) - pl
+    assert wd.shape[0] == x.shape[1] * dm
+    d = F_.conv2d(F_.pad(x, (pl, pr, pt, pb)), wd, None, stride, 0, 1, x.shape[1])
+    if rounding is not None:
+        d = rounding(d)
+    y = F_.conv2d(d, wp, b)
+    return rounding(y) if rounding is not None else y

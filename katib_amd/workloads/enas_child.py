@@ -29,6 +29,12 @@ the bf16 / tap-major weight images of the convolutions in one launch per step (`
 the convolutions then read the optimizer's images and write their weight gradients into its buffers,
 with no weight copy, accumulator fill or gradient permute of their own; one GPU only; the default
 ``module`` keeps ``torch.optim.Adam``),
+with ``--sep fused`` every ``separable_convolution`` the fused kernels serve (``ops/enas_sepconv.py``:
+``C % 8 == 0``, at most 128 filters in multiples of 16) in one launch forward - depthwise into LDS,
+pointwise on MFMA, bias on the accumulator - and one launch for the pointwise backward that recomputes the
+depthwise result, which therefore never reaches HBM and is not kept for the backward; parameter names,
+``state_dict()``, ``--optim`` and ``--head`` are untouched; the default ``split`` keeps the two layers' own
+kernels (ARCHITECTURE section 4, ``profiles/enas_sepconv.log``),
 synthetic CIFAR-10-shaped data in HBM, and data parallelism over the trial's GPUs
 (``WORLD_SIZE`` ranks, RCCL all-reduce of the flat gradient) in place of
 ``tf.distribute.MirroredStrategy``.
@@ -64,6 +70,7 @@ from ..ops import pool as hpool
 from ..ops import dwconv as hdw
 from ..ops import enas_concat as hcat
 from ..ops import enas_head as hhead
+from ..ops import enas_sepconv as hsep
 from ..ops.augment import PLAIN, AugSpec, augment_gather, cifar_lut
 from .common import CapturedStep, Timer, device, global_avg_pool, pattern_images, report
 
@@ -109,9 +116,10 @@ class _SameConv(nn.Module):
 
 
 class Op(nn.Module):
-    def __init__(self, cfg: Dict, cin: int, hw: int):
+    def __init__(self, cfg: Dict, cin: int, hw: int, sep: str = "split"):
         super().__init__()
         self.kind = cfg["opt_type"]
+        self.sep = sep
         self.identity = False
 
         # like op_library.py:51-59, parameters are read from the embedding entry's top level; the
@@ -155,7 +163,13 @@ class Op(nn.Module):
             if hpool.supported(x, self.p, self.st):  # HIP NHWC bf16 pooling (no MIOpen in the graph)
                 return hpool.pool2d(x, self.p, self.st, self.is_max)
             return self.pool(x)
-        return self.body(x if relu_done else F.relu(x))
+        x = x if relu_done else F.relu(x)
+        if self.kind == "separable_convolution" and self.sep == "fused":
+            dw, pw, bn = self.body
+            if hsep.supported(x, dw.conv.weight, pw.weight, dw.s):  # depthwise + pointwise + bias in one launch
+                return bn(hsep.separable_same(x, dw.conv.weight, pw.weight, pw.bias, dw.s,
+                                              getattr(dw, "prep", None), getattr(pw, "prep", None)))
+        return self.body(x)
 
 
 def _concat(xs: List[torch.Tensor]):
@@ -173,8 +187,10 @@ def _concat(xs: List[torch.Tensor]):
 
 
 class ChildNet(nn.Module):
-    def __init__(self, arch, nn_config):
+    def __init__(self, arch, nn_config, sep="split"):
         super().__init__()
+        if sep not in ("split", "fused"):
+            raise ValueError("sep must be 'split' or 'fused', got %r" % (sep,))
         self.arch = arch
         self.num_layers = int(nn_config["num_layers"])
         c, h, w = _chw(nn_config["input_sizes"])
@@ -187,7 +203,7 @@ class ChildNet(nn.Module):
             ins = [l - 1] + [i for i in range(l - 1) if l > 1 and skip[i] == 1]
             cin = sum(chans[i] for i in ins)
             hw = max(sizes[i] for i in ins)
-            op = Op(emb[str(opt)], cin, hw)
+            op = Op(emb[str(opt)], cin, hw, sep)
             self.ops.append(op)
             chans.append(op.cout)
             sizes.append(op.hw)
@@ -255,6 +271,9 @@ def parse_args(argv):
     p.add_argument("--optim", type=str, default="module", choices=["module", "hip"],
                    help="module = torch.optim.Adam, hip = Adam, gradient zeroing and the convolutions' weight "
                         "images in one HIP launch per step (one GPU)")
+    p.add_argument("--sep", type=str, default="split", choices=["split", "fused"],
+                   help="separable_convolution: split = depthwise and pointwise kernels with the depthwise result in "
+                        "HBM, fused = one HIP launch per direction where the fused kernels serve the layer")
     return p.parse_args(argv)
 
 
@@ -266,7 +285,7 @@ class ChildTrainer:
     ``index_select``."""
 
     def __init__(self, arch, nn_config, num_train=50000, num_valid=10000, batch_size=128, capture=True, seed=0,
-                 comm=None, data_dir="", augment=False, head="module", optim="module"):
+                 comm=None, data_dir="", augment=False, head="module", optim="module", sep="split"):
         from ..parallel.comm import Comm
 
         dev = device()
@@ -313,7 +332,7 @@ class ChildTrainer:
             spec = PLAIN
         if gather:
             self.xb = torch.empty(batch_size, h, w, c, dtype=torch.bfloat16, device=dev)
-        self.model = model = ChildNet(arch, nn_config).to(dev).to(memory_format=mf)
+        self.model = model = ChildNet(arch, nn_config, sep).to(dev).to(memory_format=mf)
         comm = self.comm
         if comm.world_size > 1:  # every rank starts from rank 0's weights
             flat0 = torch.nn.utils.parameters_to_vector(model.parameters()).detach()
@@ -431,7 +450,7 @@ def main(argv=None):
     print(">>> arch received by trial\n%s" % arch, flush=True)
     augment = bool(args.data_dir) if args.augment == "auto" else args.augment == "1"
     tr = ChildTrainer(arch, nn_config, args.num_train, args.num_valid, args.batch_size, bool(args.capture), args.seed,
-                      data_dir=args.data_dir, augment=augment, head=args.head, optim=args.optim)
+                      data_dir=args.data_dir, augment=augment, head=args.head, optim=args.optim, sep=args.sep)
     comm, dev, bs, steps = tr.comm, tr.dev, tr.bs, tr.steps
     gen = torch.Generator(device=dev).manual_seed(args.seed + comm.rank)
     timer = Timer()
