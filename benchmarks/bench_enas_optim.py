@@ -49,7 +49,9 @@ def _timed(fn):
 
 def _replaced(model, opt, segs):
     """The framework work of one ``--optim module`` step that ``ChildAdam.step()`` stands for, on buffers of
-    the same sizes: what ``_ConvFn`` / ``_DwFn`` run around their kernels, ``zero_grad`` and the fused Adam."""
+    the same sizes: what ``_ConvFn`` / ``_DwFn`` run around their kernels on a layer without a ``prep`` record
+    (the image copies, the accumulator ``zeros``, the gradient permute, ``part.sum(0)``), ``zero_grad`` and the
+    fused Adam."""
     import torch
     import torch.nn.functional as F
 

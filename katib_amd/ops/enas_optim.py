@@ -15,8 +15,11 @@ parameters into three kinds of segment (``enas_optim.h``):
   geometry) and the fp32 tap-major image ``[KK][Co]``;
 * flat - everything else, fed from the parameter's ``.grad``, which the launch zeroes.
 
-The layers find their buffers through the ``prep`` record attached to the module and run
-``_ConvPreparedFn`` / ``_DwPreparedFn``; the ``.grad`` of such a weight stays None.
+The layers find their buffers through the ``prep`` record attached to the module and hand it to
+``ops.conv._ConvFn`` / ``ops.dwconv._DwFn`` / ``ops.enas_sepconv._SepFn``, which then take their weight images
+from it and leave their weight gradients in it; the ``.grad`` of such a weight stays None. Which layers get a
+record is decided by the ``weight_supported`` of ``ops.conv`` / ``ops.dwconv``, the layer's half of the test
+their forward makes; a layer with a record raises where its forward would leave the HIP kernels.
 """
 
 from __future__ import annotations
@@ -24,7 +27,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from . import conv as hconv
+from . import conv as hconv, dwconv as hdw
 from .conv import kernels
 
 FLAT, CONV, DEPTHWISE = 0, 1, 2
@@ -112,12 +115,13 @@ class ChildAdam:
             if not isinstance(c, nn.Conv2d) or not (mod is c or hasattr(mod, "s")):
                 continue
             wname = (mname + "." if mname else "") + ("weight" if mod is c else "conv.weight")
-            Co, Cg, R, S = c.weight.shape
-            if c.groups == 1:
-                if Co % 8 == 0 and (mod is not c or (c.padding_mode == "zeros" and isinstance(c.padding, tuple))):
+            # the layer's side of what its forward asks (``supported`` there adds the input's side, and raises
+            # on a fallback once ``prep`` is attached); the depthwise kernels run unpadded only: C % 8 == 0
+            if hconv.weight_supported(c.weight, c.groups):
+                if mod is not c or (c.padding_mode == "zeros" and isinstance(c.padding, tuple)):
                     kinds[wname] = (CONV, mod)
-            elif (c.groups == c.in_channels and c.in_channels % 8 == 0 and Cg == 1 and Co // c.in_channels in (1, 2)
-                  and Co % c.in_channels == 0 and R == S and R in (3, 5, 7) and mod.s in (1, 2)):
+            elif (mod is not c and c.groups == c.in_channels and c.in_channels % 8 == 0
+                  and hdw.weight_supported(c.weight, c.groups, mod.s)):
                 kinds[wname] = (DEPTHWISE, mod)
         self.segs = []
         for name, p in params.items():

@@ -23,15 +23,15 @@ from __future__ import annotations
 import torch
 import torch.nn.functional as F_
 
-from .conv import kernels
-from .dwconv import _same
+from . import conv as hconv, dwconv as hdw
+from .conv import kernels, same_geometry
 
 
 def _geom(x, dw_weight, pw_weight, stride):
     N, C, H, W = x.shape
     Cd, _, K, _ = dw_weight.shape
-    pt, OH = _same(H, K, stride)
-    pl, OW = _same(W, K, stride)
+    pt, _, OH = same_geometry(H, K, stride)
+    pl, _, OW = same_geometry(W, K, stride)
     return [N, H, W, C, Cd // C, K, int(stride), pt, pl, OH, OW, pw_weight.shape[0]]
 
 
@@ -49,25 +49,21 @@ def supported(x: torch.Tensor, dw_weight: torch.Tensor, pw_weight: torch.Tensor,
 
 
 class _SepFn(torch.autograd.Function):
-    """Without ``prep`` records the weight images are built here, as ``_DwFn`` / ``_ConvFn`` build them, and
-    the backward returns both weight gradients. With the ``ChildAdam`` records it reads ``prep_dw.img``,
-    ``prep_pw.wk`` / ``prep_pw.wt`` and writes into ``prep_pw.g`` and ``prep_dw.partials(rows)``; the masters
-    only anchor the node, as in ``_ConvPreparedFn``, and their ``.grad`` stays None."""
+    """The weight images and the gradient sinks are those of ``_DwFn`` (depthwise) and of a 1x1 ``_ConvFn``
+    (pointwise, ``[F][Cd]``), through their helpers: built here and returned as gradients without ``prep``
+    records, the optimizer's buffers with them - the masters then only anchor the node and their ``.grad``
+    stays None."""
 
     @staticmethod
-    def forward(ctx, x, wd, wp, b, stride, prep_dw, prep_pw):
+    def forward(ctx, x, wd, wp, b, stride, prep_dw=None, prep_pw=None):
         k = kernels()
         geom = _geom(x, wd, wp, stride)
         N, H, W, C, dm, K, S, pt, pl, OH, OW, Fo = geom
         Cd = C * dm
         xn = x.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()
-        if prep_dw is None:
-            img = wd.detach().float().reshape(Cd, K * K).t().contiguous()  # [K*K][Cd] tap-major
-            wk = wp.detach().reshape(Fo, Cd).to(torch.bfloat16).contiguous()  # [F][Cd]
-            ctx.save_for_backward(xn, img, wk)
-        else:
-            img, wk = prep_dw.img, prep_pw.wk
-            ctx.save_for_backward(xn)
+        img, kept_dw = hdw._image(wd, prep_dw)
+        wk, kept_pw = hconv._image(wp.reshape(Fo, Cd), Cd, prep_pw)
+        ctx.save_for_backward(xn, *kept_dw, *kept_pw)
         y = torch.empty((N, OH, OW, Fo), device=x.device, dtype=torch.bfloat16)
         k.sep_fwd(xn, img, wk, b.detach().float().contiguous() if b is not None else None, y, geom)
         ctx.geom, ctx.prep = geom, (prep_dw, prep_pw)
@@ -84,15 +80,10 @@ class _SepFn(torch.autograd.Function):
         dev = gy.device
         gyn = gy.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()
         gx = gwd = gwp = gb = None
-        if prep_dw is None:
-            xn, img, wk = ctx.saved_tensors
-            wt = wk.t().contiguous()  # [Cd][F]
-            acc = torch.zeros((Fo, Cd), device=dev, dtype=torch.float32)
-        else:
-            xn, = ctx.saved_tensors
-            img, wt, acc = prep_dw.img, prep_pw.wt, prep_pw.g.view(Fo, Cd)
-            if wt is None:
-                raise RuntimeError("fused separable conv: the optimizer holds no [Cd][F] image for the pointwise layer")
+        xn, *kept = ctx.saved_tensors
+        img = hdw._kept_image(kept[:1], prep_dw)
+        wt = hconv._image_t(kept[1:], prep_pw)  # [Cd][F]
+        acc, own_pw = hconv._sink(prep_pw, Fo, Cd, dev)
         gd = torch.empty((N, OH, OW, Cd), device=dev, dtype=torch.bfloat16)
         k.sep_bwd_pw(xn, img, wt, gyn, gd, acc, ctx.geom)
         if ctx.needs_input_grad[0]:
@@ -100,15 +91,13 @@ class _SepFn(torch.autograd.Function):
             k.dw_dgrad(gd, img, dx, dwgeom)
             gx = dx.permute(0, 3, 1, 2)
         rows = k.dw_wgrad_rows(dwgeom)
-        if prep_dw is not None:
-            k.dw_wgrad(xn, gd, prep_dw.partials(rows), dwgeom)
-        else:
-            if ctx.needs_input_grad[1]:
-                part = torch.empty((rows, Cd, K * K), device=dev, dtype=torch.float32)
-                k.dw_wgrad(xn, gd, part, dwgeom)
+        if prep_dw is not None or ctx.needs_input_grad[1]:  # the optimizer's partials are always fed
+            part, own = hdw._sink(prep_dw, rows, Cd, K * K, dev)
+            k.dw_wgrad(xn, gd, part, dwgeom)
+            if own:
                 gwd = part.sum(0).view(wd_shape).to(wd_dtype)
-            if ctx.needs_input_grad[2]:
-                gwp = acc.view(wp_shape).to(wp_dtype)
+        if own_pw and ctx.needs_input_grad[2]:
+            gwp = acc.view(wp_shape).to(wp_dtype)
         if has_b and ctx.needs_input_grad[3]:  # HIP channel sum: no PyTorch reduction under capture
             gb = torch.empty(Fo, device=dev, dtype=torch.float32)
             k.channel_sum(gyn.view(-1, Fo), gb)
@@ -150,10 +139,8 @@ def reference(x, wd, wp, b, stride, dm, rounding=None):
     ``wp`` ``[F, C*dm, 1, 1]``, ``b`` ``[F]`` or None. ``rounding`` (:func:`round_bf16`) is applied to ``d`` -
     whose gradient is ``gd`` - and to ``y``: the kernels' rounding points."""
     K = wd.shape[-1]
-    pt, OH = _same(x.shape[2], K, stride)
-    pl, OW = _same(x.shape[3], K, stride)
-    pb = max((OH - 1) * stride + K - x.shape[2], 0) - pt
-    pr = max((OW - 1) * stride + K - x.shape[3], 0) - pl
+    pt, pb, _ = same_geometry(x.shape[2], K, stride)
+    pl, pr, _ = same_geometry(x.shape[3], K, stride)
     assert wd.shape[0] == x.shape[1] * dm
     d = F_.conv2d(F_.pad(x, (pl, pr, pt, pb)), wd, None, stride, 0, 1, x.shape[1])
     if rounding is not None:

@@ -89,12 +89,6 @@ FUSED_INPUT = False
 PAD8_INPUT = False
 
 
-def _same_pad(size: int, k: int, s: int):
-    out = -(-size // s)
-    total = max((out - 1) * s + k - size, 0)
-    return total // 2, total - total // 2, out
-
-
 class _SameConv(nn.Module):
     """TF/Keras ``padding='same'`` convolution (asymmetric padding for even kernels / strides)."""
 
@@ -110,8 +104,9 @@ class _SameConv(nn.Module):
             return hconv.same_conv2d(x, c.weight, c.bias, self.s, prep)
         if c.groups > 1 and hdw.supported(x, c.weight, c.groups, self.s):  # HIP depthwise (NHWC) path
             return hdw.depthwise_same(x, c.weight, c.bias, self.s, prep)
-        t, b, _ = _same_pad(x.shape[2], self.k, self.s)
-        l, r, _ = _same_pad(x.shape[3], self.k, self.s)
+        hconv._prep_guard(self, x)
+        t, b, _ = hconv.same_geometry(x.shape[2], self.k, self.s)
+        l, r, _ = hconv.same_geometry(x.shape[3], self.k, self.s)
         return self.conv(F.pad(x, (l, r, t, b)))
 
 
