@@ -202,8 +202,9 @@ void dwpw_fwd_multi(std::vector<py::tuple> calls) {
   }
 }
 
-// (x, pw, z, stats|None, co_off, off)
-void pw_fwd(std::vector<py::tuple> calls, int64_t S) {
+// (x, pw, z, stats|None, co_off, off[, S]): entries may differ in every shape and, with a 7th field, in
+// stride (the two preprocess layers of a cell: a FactorizedReduce next to a plain 1x1)
+void pw_fwd(std::vector<py::tuple> calls, int64_t S0) {
   check_batch<PwFwdBatch>(calls);
   PwFwdBatch bt{};
   bt.n = calls.size();
@@ -212,6 +213,8 @@ void pw_fwd(std::vector<py::tuple> calls, int64_t S) {
     Tensor x = t[0].cast<Tensor>(), pw = t[1].cast<Tensor>(), z = t[2].cast<Tensor>();
     OptT stats = t[3].cast<OptT>();
     const int co_off = t[4].cast<int>(), off = t[5].cast<int>();
+    const int64_t S = t.size() > 6 ? t[6].cast<int64_t>() : S0;
+    TORCH_CHECK(S == 1 || S == 2, "pw_fwd stride must be 1 or 2");
     check_f32(x, "x"); check_f32(pw, "pw"); check_z(z, "z");
     // a 5-D x is node-major [nodes][N][C / nodes][H][W] (a DARTS cell output kept as its nodes' buffers)
     const bool nm = x.dim() == 5;
@@ -229,7 +232,6 @@ void pw_fwd(std::vector<py::tuple> calls, int64_t S) {
       TORCH_CHECK(stats->scalar_type() == at::kDouble && stats->numel() >= kRep * 2 * z.size(1), "stats [kRep][2Ctot]");
     a.N = N; a.Cin = Cin; a.Cout = Cout; a.CoutTotal = z.size(1); a.co_off = co_off;
     a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.S = S; a.off = off; a.relu = 1; a.xnodes = xnodes;
-    SAME_SHAPE(bt, N); SAME_SHAPE(bt, Cin); SAME_SHAPE(bt, Cout); SAME_SHAPE(bt, Ho); SAME_SHAPE(bt, Wo);
   }
   launch_pw_fwd(bt, cur_stream());
 }
@@ -264,18 +266,25 @@ void pool_fwd_multi(std::vector<py::tuple> calls) {
   launch_pool_fwd_multi(bt, cur_stream());
 }
 
-// calls: per edge (zs, bns, widx, w|None, id_idx, xid|None, upd); all edges summed into `out`
-void combine_fwd(std::vector<py::tuple> calls, OptT gamma, OptT beta, Tensor out, double momentum,
+// calls: per edge (zs, bns, widx, w|None, id_idx, xid|None, upd); all edges summed into `out`.
+// Entries with an 8th field (..., own out) are independent instead: each is the BN-apply of ONE op
+// into its own output of its own shape (no softmax weight, identity, affine part or accumulation) -
+// a cell's two preprocess layers in one launch; `out` is then the first entry's.
+void combine_fwd(std::vector<py::tuple> calls, OptT gamma, OptT beta, Tensor out0, double momentum,
                  bool update_running, bool accumulate) {
-  check_f32(out, "out");
   check_batch<CombineFwdBatch>(calls);
   CombineFwdBatch bt{};
   bt.n = calls.size();
-  const int C = out.size(1);
-  TORCH_CHECK(C <= kMaxC, "C too large");
-  TORCH_CHECK((int64_t)2 * bt.n * kMaxOps * C * 4 <= 65536, "combine LDS budget exceeded");
+  const bool each = calls[0].size() > 7;
   for (int e = 0; e < bt.n; ++e) {
     const py::tuple& t = calls[e];
+    TORCH_CHECK((t.size() > 7) == each, "combine_fwd: summed and independent entries do not mix");
+    Tensor out = each ? t[7].cast<Tensor>() : out0;
+    check_f32(out, "out");
+    TORCH_CHECK(out.dim() == 4, "out must be NCHW");
+    const int C = out.size(1);
+    TORCH_CHECK(C <= kMaxC, "C too large");
+    TORCH_CHECK((int64_t)2 * bt.n * kMaxOps * C * 4 <= 65536, "combine LDS budget exceeded");
     auto zs = t[0].cast<std::vector<Tensor>>();
     auto bns = t[1].cast<std::vector<py::tuple>>();
     auto widx = t[2].cast<std::vector<int64_t>>();
@@ -305,11 +314,15 @@ void combine_fwd(std::vector<py::tuple> calls, OptT gamma, OptT beta, Tensor out
     a.gamma = ptr_or_null<float>(gamma); a.beta = ptr_or_null<float>(beta);
     a.out = out.data_ptr<float>(); a.momentum = momentum; a.update_running = update_running;
     a.accumulate = accumulate;
+    a.each = each;
+    if (each)
+      TORCH_CHECK(a.nops == 1 && a.nupd == 0 && !a.w && !a.xid && !a.gamma && !a.beta && !accumulate,
+                  "an independent combine_fwd entry is one op's plain BN-apply");
   }
   launch_combine_fwd(bt, cur_stream());
 }
 
-// (dout, zs, bns, xid|None, red, widx, id_idx, gw|None)
+// (dout, zs, bns, xid|None, red, widx, id_idx, gw|None); entries may differ in N, C and HW
 void combine_bwd_reduce(std::vector<py::tuple> calls) {
   check_batch<CombineBwdBatch>(calls);
   CombineBwdBatch bt{};
@@ -349,7 +362,6 @@ void combine_bwd_reduce(std::vector<py::tuple> calls) {
       }
       TORCH_CHECK(id_idx < a.gwstride, "id_idx out of range");
     }
-    SAME_SHAPE(bt, N); SAME_SHAPE(bt, C); SAME_SHAPE(bt, HW);
   }
   launch_combine_bwd_reduce(bt, cur_stream());
 }

@@ -102,6 +102,7 @@ struct PwFwdArgs {
   int N, Cin, Cout, CoutTotal, co_off, H, W, Ho, Wo, S, off;
   int relu;  // 1: input = relu(x) (StdConv / FactorizedReduce); 0: identity (pointwise half of a dw-pw stage)
   int xnodes;  // relu: x node-major [xnodes][N][Cin / xnodes][H][W] when > 1 (a cell output kept as its nodes)
+  int nblk;    // pw_fwd_kernel: workgroups of this entry (grid.x is the max over entries; set by launch_pw_fwd)
 };
 
 struct PoolFwdArgs {
@@ -115,6 +116,9 @@ struct CombineFwdArgs {
   BNRef upd[kMaxUpd]; int nupd;  // extra BN layers whose running stats are updated here (not summed)
   const float* w; int id_idx; const float* xid; const float* gamma; const float* beta;
   float* out; int N, C, HW; float momentum; int update_running; int accumulate;
+  // each: an independent entry (blockIdx.y) with its own out / N / C / HW - one op, no softmax weight, no
+  // identity (the BN-apply of a cell's two preprocess layers in one launch) - on nblk workgroups
+  int each, nblk;
 };
 
 struct CombineBwdArgs {
@@ -122,6 +126,7 @@ struct CombineBwdArgs {
   const float* xid; double* red; int N, C, HW;  // red: kRep replicas of [(nops+1)*C + 1]
   double* gw; int widx[kMaxOps]; int id_idx;  // optional: d(loss)/d(softmax weight), kRep replicas of [nw]
   int rstride, gwstride;
+  int nblk;  // workgroups of this entry (grid.x is the max over entries; set by launch_combine_bwd_reduce)
 };
 
 struct PwBwdArgs {

@@ -222,14 +222,72 @@ __global__ void __launch_bounds__(256) combine_fwd_kernel(CombineFwdBatch bt) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// combine_fwd, independent entries (blockIdx.y): out_e = BN_e(z_e), running stats of entry e updated.
+// The BN-apply of a cell's two preprocess layers, which share nothing but the launch: each entry has
+// its own shape and runs on its first nblk workgroups. Coefficients and rounding as the summed
+// kernel's single-entry case (same helpers per statistics form, w = 1), so the output is the same.
+// ------------------------------------------------------------------------------------------------
+template <bool V4>
+__global__ void __launch_bounds__(256) combine_fwd_each_kernel(CombineFwdBatch bt) {
+  const CombineFwdArgs& a = bt.e[blockIdx.y];
+  if ((int)blockIdx.x >= a.nblk) return;
+  const int C = a.C, HW = a.HW;
+  const size_t total = (size_t)a.N * C * HW, total4 = total / 4;
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* sMean = smem;    // [C]
+  float* sInv = smem + C;  // [C]
+  typedef float f4 __attribute__((ext_vector_type(4)));
+  const BNRef& b = a.bn[0];
+  const zt* z = a.z[0];
+  size_t i4 = (size_t)blockIdx.x * 256 + threadIdx.x;
+  f4 zv = {0.f, 0.f, 0.f, 0.f};
+  const bool coop = !b.eval && b.rep > 1;  // unfolded statistics (their fold joins the cell's first node's)
+  const bool split = !coop && kMaxOps * C <= 256;
+  BnRaw raw{0.0, 0.0, 0.f, 1.f};
+  if (split && (int)threadIdx.x < C) raw = bn_raw(b, threadIdx.x);
+  if (V4 && i4 < total4) zv = zld4(z + 4 * i4);  // in flight with the statistic loads
+  if (split) {
+    if ((int)threadIdx.x < C) bn_finish(b, raw, sMean[threadIdx.x], sInv[threadIdx.x]);
+  } else if (coop) {
+    bn_coeffs_coop(b, 0, C, sMean, sInv);
+  } else {
+    for (int c = threadIdx.x; c < C; c += 256) bn_coeffs(b, c, sMean[c], sInv[c]);
+  }
+  __syncthreads();
+  if (a.update_running && b.rmean && !b.eval)
+    for (int c = blockIdx.x * 256 + threadIdx.x; c < C; c += a.nblk * 256) {
+      double m, v;
+      bn_moments(b, c, m, v);
+      double cnt = 1.0 / (double)b.inv_count;
+      double vu = cnt > 1 ? v * cnt / (cnt - 1) : v;
+      b.rmean[c] = (1.f - a.momentum) * b.rmean[c] + a.momentum * (float)m;
+      b.rvar[c] = (1.f - a.momentum) * b.rvar[c] + a.momentum * (float)vu;
+    }
+  if (V4) {
+    for (bool first = true; i4 < total4; i4 += (size_t)a.nblk * 256, first = false) {
+      const int c = (int)((i4 * 4 / HW) % C);
+      if (!first) zv = zld4(z + 4 * i4);
+      reinterpret_cast<f4*>(a.out)[i4] = (zv - sMean[c]) * sInv[c];
+    }
+    return;
+  }
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)a.nblk * 256) {
+    const int c = (int)((i / HW) % C);
+    a.out[i] = (z2f(z[i]) - sMean[c]) * sInv[c];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // combine_bwd_reduce: S1[c] = sum dout, S2[k][c] = sum dout * zhat_k, Sid = sum dout * x
-// One block per (n, c) plane.
+// One block per (n, c) plane. Entries may differ in N, C and HW (a cell's two preprocess layers):
+// entry e runs on its first e.nblk workgroups (a multiple of its C).
 // ------------------------------------------------------------------------------------------------
 template <bool V4>
 __global__ void __launch_bounds__(256) combine_bwd_reduce_kernel(CombineBwdBatch bt) {
   const CombineBwdArgs& a = bt.e[blockIdx.y];
+  if ((int)blockIdx.x >= a.nblk) return;
   const int C = a.C, HW = a.HW;
-  const int c = blockIdx.x % C, g0 = blockIdx.x / C, G = gridDim.x / C;
+  const int c = blockIdx.x % C, g0 = blockIdx.x / C, G = a.nblk / C;
   __shared__ float sMean[kMaxOps], sInv[kMaxOps];
   __shared__ float part[4][kMaxOps + 2];
   if (threadIdx.x < a.nops) bn_coeffs(a.bn[threadIdx.x], c, sMean[threadIdx.x], sInv[threadIdx.x]);
@@ -315,6 +373,23 @@ void launch_combine_fwd(const CombineFwdBatch& b, hipStream_t st) {
   const CombineFwdArgs& a = b.e[0];
   size_t total = (size_t)a.N * a.C * a.HW;
   auto al16 = [](const void* p) { return p == nullptr || reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+  if (a.each) {  // independent entries: the vector path if every entry can take it, workgroups per entry
+    CombineFwdBatch m = b;
+    bool v4 = true;
+    for (int e = 0; e < m.n; ++e) v4 = v4 && m.e[e].HW % 4 == 0 && al16(m.e[e].out) && al16(m.e[e].z[0]);
+    int maxblk = 1, maxc = 0;
+    for (int e = 0; e < m.n; ++e) {
+      CombineFwdArgs& x = m.e[e];
+      const size_t tot = (size_t)x.N * x.C * x.HW;
+      x.nblk = (int)std::max<size_t>(1, std::min<size_t>(((v4 ? tot / 4 : tot) + 255) / 256, (size_t)max_blocks() / m.n));
+      maxblk = std::max(maxblk, x.nblk);
+      maxc = std::max(maxc, x.C);
+    }
+    const size_t lds = sizeof(float) * 2 * maxc;
+    if (v4) hipLaunchKernelGGL(combine_fwd_each_kernel<true>, dim3(maxblk, m.n), dim3(256), lds, st, m);
+    else hipLaunchKernelGGL(combine_fwd_each_kernel<false>, dim3(maxblk, m.n), dim3(256), lds, st, m);
+    return;
+  }
   bool v4 = a.HW % 4 == 0 && al16(a.out);
   for (int e = 0; e < b.n && v4; ++e) {
     v4 = al16(b.e[e].xid);
@@ -327,19 +402,22 @@ void launch_combine_fwd(const CombineFwdBatch& b, hipStream_t st) {
 }
 
 void launch_combine_bwd_reduce(const CombineBwdBatch& b, hipStream_t st) {
-  const CombineBwdArgs& a = b.e[0];
-  bool v4 = a.HW % 4 == 0;
-  for (int e = 0; e < b.n; ++e) {
-    const CombineBwdArgs& x = b.e[e];
+  CombineBwdBatch m = b;
+  bool v4 = true;
+  int maxblk = 1;
+  for (int e = 0; e < m.n; ++e) {
+    CombineBwdArgs& x = m.e[e];
     uintptr_t bits = (uintptr_t)x.dout | (uintptr_t)x.xid;
     for (int k = 0; k < x.nops; ++k) bits |= (uintptr_t)x.z[k];
-    v4 &= (bits & 15) == 0;
+    v4 &= x.HW % 4 == 0 && (bits & 15) == 0;
+    // half the persistent-grid budget: two images per workgroup at B5 sizes, so each thread keeps two
+    // elements' operands in flight and the coefficient prologue / reduction tail are paid half as often
+    x.nblk = x.C * channel_groups(x.N, x.C, 2 * m.n);
+    maxblk = std::max(maxblk, x.nblk);
   }
-  // half the persistent-grid budget: two images per workgroup at B5 sizes, so each thread keeps two
-  // elements' operands in flight and the coefficient prologue / reduction tail are paid half as often
-  const dim3 grid(a.C * channel_groups(a.N, a.C, 2 * b.n), b.n);
-  if (v4) hipLaunchKernelGGL(combine_bwd_reduce_kernel<true>, grid, dim3(256), 0, st, b);
-  else hipLaunchKernelGGL(combine_bwd_reduce_kernel<false>, grid, dim3(256), 0, st, b);
+  const dim3 grid(maxblk, m.n);
+  if (v4) hipLaunchKernelGGL(combine_bwd_reduce_kernel<true>, grid, dim3(256), 0, st, m);
+  else hipLaunchKernelGGL(combine_bwd_reduce_kernel<false>, grid, dim3(256), 0, st, m);
 }
 
 __global__ void __launch_bounds__(256) fold_rows_kernel(FoldArgs a) {

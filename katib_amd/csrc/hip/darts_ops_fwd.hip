@@ -244,16 +244,31 @@ static bool try_pw_fwd_wave(const PwFwdBatch& b, hipStream_t st) {
 
 void launch_pw_fwd(const PwFwdBatch& b, hipStream_t st) {
   const PwFwdArgs& a = b.e[0];
+  // the wave kernels size their grid from the first entry: only for entries of one shape
+  bool same = true;
+  for (int e = 1; e < b.n; ++e) {
+    const PwFwdArgs& x = b.e[e];
+    same = same && x.N == a.N && x.Cin == a.Cin && x.Cout == a.Cout && x.Ho == a.Ho && x.Wo == a.Wo;
+  }
   // (narrow layers stay on the 64-pixel tiles below: a pixel-quad-per-thread kernel had too few
   // waves at B5 sizes - 32-128 workgroups - and measured 333 vs 281 us per step,
   // profiles/darts_vec_ab_r04.log)
-  if (try_pw_fwd_wave<48, 16>(b, st) || try_pw_fwd_wave<48, 32>(b, st) || try_pw_fwd_wave<64, 32>(b, st) ||
-      try_pw_fwd_wave<32, 16>(b, st) || try_pw_fwd_wave<16, 16>(b, st) || try_pw_fwd_wave<32, 32>(b, st) ||
-      try_pw_fwd_wave<64, 64>(b, st) || try_pw_fwd_wave<128, 64>(b, st))  // 128 -> 64: last-cell preprocess
+  if (same &&
+      (try_pw_fwd_wave<48, 16>(b, st) || try_pw_fwd_wave<48, 32>(b, st) || try_pw_fwd_wave<64, 32>(b, st) ||
+       try_pw_fwd_wave<32, 16>(b, st) || try_pw_fwd_wave<16, 16>(b, st) || try_pw_fwd_wave<32, 32>(b, st) ||
+       try_pw_fwd_wave<64, 64>(b, st) || try_pw_fwd_wave<128, 64>(b, st)))  // 128 -> 64: last-cell preprocess
     return;
-  size_t lds = sizeof(float) * (a.Cin * 64 + 2 * a.Cout);
-  dim3 grid(per_edge_blocks(a.N * a.Ho * a.Wo / 64, b.n), b.n);
-  hipLaunchKernelGGL(pw_fwd_kernel, grid, dim3(256), lds, st, b);
+  // every entry gets the workgroups its own tile count asks for; grid.x and the LDS are the largest entry's
+  PwFwdBatch m = b;
+  int maxblk = 1;
+  size_t lds = 0;
+  for (int e = 0; e < m.n; ++e) {
+    PwFwdArgs& x = m.e[e];
+    x.nblk = per_edge_blocks(x.N * x.Ho * x.Wo / 64, m.n);
+    maxblk = std::max(maxblk, x.nblk);
+    lds = std::max(lds, sizeof(float) * (x.Cin * 64 + 2 * x.Cout));
+  }
+  hipLaunchKernelGGL(pw_fwd_kernel, dim3(maxblk, m.n), dim3(256), lds, st, m);
 }
 
 }  // namespace katib_hip

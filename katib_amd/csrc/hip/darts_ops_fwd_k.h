@@ -478,10 +478,12 @@ __global__ void __launch_bounds__(256) pw_fwd_wave_kernel(PwFwdBatch bt) {
 
 // ------------------------------------------------------------------------------------------------
 // pw_fwd: z[:, co_off + co] = pw . relu(x) at (oy*S + off, ox*S + off); StdConv / FR half
-// grid: N*Ho*Wo/64 blocks of 64-pixel tiles; Cin, Cout <= 256
+// grid: N*Ho*Wo/64 blocks of 64-pixel tiles; Cin, Cout <= 256. Entries may differ in every shape
+// (a cell's two preprocess layers in one launch): entry e runs on its first e.nblk workgroups
 // ------------------------------------------------------------------------------------------------
 static __global__ void __launch_bounds__(256) pw_fwd_kernel(PwFwdBatch bt) {
   const PwFwdArgs& a = bt.e[blockIdx.y];
+  if ((int)blockIdx.x >= a.nblk) return;
   constexpr int P = 64;
   const int Cin = a.Cin, Cout = a.Cout, H = a.H, W = a.W, Ho = a.Ho, Wo = a.Wo;
   const int HWo = Ho * Wo;
@@ -491,7 +493,7 @@ static __global__ void __launch_bounds__(256) pw_fwd_kernel(PwFwdBatch bt) {
   float* sStat = sX + Cin * P;   // [2*Cout]
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   for (int i = tid; i < 2 * Cout; i += 256) sStat[i] = 0.f;
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+  for (int t = blockIdx.x; t < ntiles; t += a.nblk) {
     const int pix0 = t * P;  // flat over N*Ho*Wo (HWo % 64 == 0)
     const int n = pix0 / HWo, prem = pix0 % HWo;
     #pragma unroll 4  // keep several global loads of the staging pass in flight

@@ -802,12 +802,16 @@ def _dims(x: torch.Tensor):
     return tuple(x.shape)
 
 
-def _stdconv_forward(x, rm, rv, training, momentum, eps, w1, w2, defer=None):
-    """ReLU -> 1x1 conv (ReLUConvBN, operations.py) or FactorizedReduce (two stride-2 1x1
-    convs on offset grids, channel-concatenated) -> BN(affine=False). Returns (out, state).
-    ``defer`` (a list, inside a cell): the BN statistics are not folded here - the BN-apply reads
-    the replicas itself and the fold segment is appended to ``defer`` for the cell's first node's
-    fold; the backward then reads them folded."""
+# The two preprocess layers of a cell read and write nothing of each other's: their pointwise
+# convolutions go out as one pw_fwd launch, their BN-applies as one combine_fwd launch of independent
+# entries, their BN-backward sums as one combine_bwd_reduce launch (module attribute, flipped between
+# steps by tests and A/B runs; profiles/darts_pre_pair_bench_ab.txt).
+PAIR_PRE = True
+
+
+def _stdconv_prep(x, rm, rv, training, eps, w1, w2):
+    """Buffers and launch entries of one preprocess layer: (pw_fwd entries with their stride, fold
+    segment of the statistics or None, combine_fwd entry without its BN reference, out, state)."""
     x = x.contiguous()
     N, Cin, H, W = _dims(x)
     fr = w2 is not None
@@ -817,36 +821,90 @@ def _stdconv_forward(x, rm, rv, training, momentum, eps, w1, w2, defer=None):
     stats = zeros64(REP * 2 * Cout, x.device) if training else None
     z = torch.empty(N, Cout, Ho, Wo, device=x.device, dtype=ZDT)
     if fr:
-        _K.pw_fwd([(x, w1, z, stats, 0, 0), (x, w2, z, stats, Cout // 2, 1)], 2)
+        ents = [(x, w1, z, stats, 0, 0, 2), (x, w2, z, stats, Cout // 2, 1, 2)]
     else:
-        _K.pw_fwd([(x, w1, z, stats, 0, 0)], 1)
+        ents = [(x, w1, z, stats, 0, 0, 1)]
     bn = _bn(stats, rm, rv, cnt, training, eps, Cout)
+    out = torch.empty(z.shape, device=x.device)
+    return ents, (stats, 2 * Cout, 2 * Cout) if training else None, out, (x, z, w1, w2, bn, fr, Cout, training)
+
+
+def _pre_pairable(layers) -> bool:
+    """``layers``: (x, w1, w2) of a cell's preprocess layers. One pw_fwd launch takes them when every
+    entry runs the narrow tile kernel (fewer than 16 channels in and out) or when they share every
+    shape; the 16..64-channel wave kernels size their grid for one shape."""
+    if all(max(_dims(x)[1], w1.shape[0]) < 16 for x, w1, _ in layers):
+        return True
+    x0, w0, v0 = layers[0]
+    return all(_dims(x) == _dims(x0) and w1.shape == w0.shape and (w2 is None) == (v0 is None) for x, w1, w2 in layers)
+
+
+def _stdconv_forward(x, rm, rv, training, momentum, eps, w1, w2, defer=None):
+    """ReLU -> 1x1 conv (ReLUConvBN, operations.py) or FactorizedReduce (two stride-2 1x1
+    convs on offset grids, channel-concatenated) -> BN(affine=False). Returns (out, state).
+    ``defer`` (a list, inside a cell): the BN statistics are not folded here - the BN-apply reads
+    the replicas itself and the fold segment is appended to ``defer`` for the cell's first node's
+    fold; the backward then reads them folded."""
+    ents, seg, out, state = _stdconv_prep(x, rm, rv, training, eps, w1, w2)
+    z, bn = state[1], state[4]
+    _K.pw_fwd(ents, ents[0][6])
     late = defer is not None and training and _defer()
     if training and not late:
-        _fold([(stats, 2 * Cout, 2 * Cout)])
+        _fold([seg])
     if late:
-        defer.append((stats, 2 * Cout, 2 * Cout))
-    out = torch.empty(z.shape, device=x.device)
+        defer.append(seg)
     _K.combine_fwd([([z], [_unfolded(bn) if late else bn], [0], None, -1, None, [])], None, None, out, momentum,
                    training, False)
-    return out, (x, z, w1, w2, bn, fr, Cout, training)
+    return out, state
 
 
-def _stdconv_backward(state, dout, need_x, sinks, keys, gx=None, first=True):
+def _stdconv_forward_pair(layers, training, momentum, eps, defer):
+    """:func:`_stdconv_forward` of a cell's preprocess layers ``(x, rm, rv, w1, w2)`` in one pw_fwd
+    launch and one BN-apply launch (independent combine_fwd entries); under SyncBN their statistics
+    share one fold - one rendezvous. Returns [(out, state), ...]."""
+    preps = [_stdconv_prep(x, rm, rv, training, eps, w1, w2) for x, rm, rv, w1, w2 in layers]
+    _K.pw_fwd([e for ents, _, _, _ in preps for e in ents], 1)
+    late = training and _defer()
+    if late:
+        defer.extend(seg for _, seg, _, _ in preps)
+    elif training:
+        _fold([seg for _, seg, _, _ in preps])
+    calls = [([st[1]], [_unfolded(st[4]) if late else st[4]], [0], None, -1, None, [], out) for _, _, out, st in preps]
+    _K.combine_fwd(calls, None, None, calls[0][7], momentum, training, False)
+    return [(out, st) for _, _, out, st in preps]
+
+
+def _stdconv_reduce(pairs):
+    """The BN-backward sums of preprocess layers, ``pairs`` = [(state, dout), ...], in one
+    combine_bwd_reduce launch (and, not deferred, one fold). Returns their ``red`` buffers."""
+    reds, calls, segs = [], [], []
+    for (x, z, _, _, bn, _, Cout, training), dout in pairs:
+        nred = 2 * Cout + 1
+        red = zeros64(REP * nred, x.device)
+        reds.append(red)
+        if training:
+            calls.append((dout, [z], [bn], None, red, [0], -1, None))
+            segs.append((red, nred, nred))
+    if calls:
+        _K.combine_bwd_reduce(calls)
+        # deferred: the pointwise backward (its only consumer) sums the replicas in its prologue, and
+        # nothing reads them later, so this fold goes away (the arena is re-zeroed every step)
+        if not _defer():
+            _fold(segs)
+    return reds
+
+
+def _stdconv_backward(state, dout, need_x, sinks, keys, gx=None, first=True, red=None):
     """Returns the input gradient (or None); weight gradients through ``sinks``. ``gx`` (shaped
     like the input, maybe node-major): write the input gradient there - overwriting it when
-    ``first``, else adding to it - instead of into a new buffer."""
+    ``first``, else adding to it - instead of into a new buffer. ``red``: the layer's BN-backward
+    sums, already launched by :func:`_stdconv_reduce` on this (contiguous) ``dout``."""
     x, z, w1, w2, bn, fr, Cout, training = state
     dout = dout.contiguous()
     nred = 2 * Cout + 1
-    red = zeros64(REP * nred, x.device)
-    # deferred: the pointwise backward (its only consumer) sums the replicas in its prologue, and
-    # nothing reads them later, so this fold goes away (the arena is re-zeroed every step)
+    if red is None:
+        red = _stdconv_reduce([(state, dout)])[0]
     late = training and _defer()
-    if training:
-        _K.combine_bwd_reduce([(dout, [z], [bn], None, red, [0], -1, None)])
-        if not late:
-            _fold([(red, nred, nred)])
     gs = (dout, z, red[:Cout], red[Cout:2 * Cout], bn, None, 0, REP if late else 1, nred)
     g1, s1 = sinks.get(w1, keys[0])
     given = gx is not None
@@ -962,14 +1020,15 @@ def _cell_fwd(spec, s0, s1, wts, P, bn_of, training, momentum, eps, grad=True):
     concatenated (the next cells' preprocess and the head read it node-major)."""
     late = []  # preprocess BN statistics folded by the first node's fold
 
-    def pre(x, p):
+    def layer(x, p):
         kind, pnames, bname = p
-        rm, rv = bn_of(bname)
-        if kind == "fr":
-            return _stdconv_forward(x, rm, rv, training, momentum, eps, P[pnames[0]], P[pnames[1]], late)
-        return _stdconv_forward(x, rm, rv, training, momentum, eps, P[pnames[0]], None, late)
-    t0, st0 = pre(s0, spec.pre0)
-    t1, st1 = pre(s1, spec.pre1)
+        return (x,) + tuple(bn_of(bname)) + (P[pnames[0]], P[pnames[1]] if kind == "fr" else None)
+    layers = [layer(s0, spec.pre0), layer(s1, spec.pre1)]
+    if PAIR_PRE and _pre_pairable([(x, w1, w2) for x, _, _, w1, w2 in layers]):
+        (t0, st0), (t1, st1) = _stdconv_forward_pair(layers, training, momentum, eps, late)
+    else:
+        (t0, st0), (t1, st1) = [_stdconv_forward(x, rm, rv, training, momentum, eps, w1, w2, late)
+                                for x, rm, rv, w1, w2 in layers]
     states = [t0, t1]
     N, C = t0.shape[0], spec.C
     nn_ = len(spec.nodes)
@@ -1086,13 +1145,18 @@ def _cell_bwd(state, gO, sinks, pkey, gx0, first0, gx1, first1, need0, need1, al
         elif alpha_need:
             ga_rows[i] = [e.gw[:wts.shape[1]] for e in edges]
     gs = [None, None]
+    pres = []
     for j, (st, needx, gx, fst, pre) in enumerate(((st0, need0, gx0, first0, spec.pre0),
                                                    (st1, need1, gx1, first1, spec.pre1))):
         if not need[j]:  # neither its input nor its weights need a gradient: nothing to launch
             continue
         if first[j]:  # only "none" primitives read this state
             gS[j] = torch.zeros_like(states[j])
-        gs[j] = _stdconv_backward(st, gS[j], needx, sinks, tuple(pkey(n) for n in pre[1]) + (None,), gx, fst)
+        pres.append((j, st, gS[j].contiguous(), needx, gx, fst, pre))
+    # both layers' BN-backward sums in one launch (neither reads what the other's backward writes)
+    reds = _stdconv_reduce([(st, dout) for _, st, dout, _, _, _, _ in pres]) if PAIR_PRE else [None] * len(pres)
+    for (j, st, dout, needx, gx, fst, pre), red in zip(pres, reds):
+        gs[j] = _stdconv_backward(st, dout, needx, sinks, tuple(pkey(n) for n in pre[1]) + (None,), gx, fst, red)
     gw = None
     if alpha_rows is None and alpha_need:
         if cell_gw:
