@@ -110,7 +110,7 @@ _VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_TU_FLAGS = {"transformer.hip": _VGPR_FORM, "darts_ops_fwd.hip": _VGPR_FORM, "darts_ops_pwb.hip": _VGPR_FORM,
                 "enas_concat.hip": _NO_PK_F32, "enas_head.hip": _NO_PK_F32, "enas_optim.hip": _NO_PK_F32,
-                "enas_sepconv.hip": _NO_PK_F32}
+                "enas_sepconv.hip": _NO_PK_F32, "enas_fanin.hip": _NO_PK_F32}
 
 
 def hip_target() -> str:

@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "enas_ctrl.h"
+#include "enas_fanin.h"
 #include "enas_optim.h"
 
 using at::Tensor;
@@ -213,9 +214,72 @@ void adam(const Tensor& table, int64_t nseg, int64_t tiles, const Tensor& counte
               "enas_adam launch failed");
 }
 
+// ---- the child's gradient fan-in (enas_fanin.hip)
+namespace EF = katib_hip::enasfanin;
+
+void fanin_t(const Tensor& t, const Tensor& gx, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == gx.device() && t.scalar_type() == at::kBFloat16 && t.dim() == 4, "enas_fanin: ",
+              name, " must be a 4-D bf16 tensor on the GPU of gx");
+}
+
+// x [B, H, H, C] (None when no term has a ReLU), gx like it; terms = (g, off, relu) with g [B, m, m, Cg] read in
+// place: channels adjacent, pixels gs >= Cg elements apart, rows and images dense over that stride
+void enas_fanin(const c10::optional<Tensor>& x, const std::vector<py::tuple>& terms, const Tensor& gx) {
+  TORCH_CHECK(gx.defined() && gx.dim() == 4, "enas_fanin: gx is [B, H, H, C]");
+  fanin_t(gx, gx, "gx");
+  const int64_t B = gx.size(0), H = gx.size(1), C = gx.size(3);
+  TORCH_CHECK(gx.is_contiguous() && gx.size(2) == H && gx.numel() > 0 && C % 8 == 0,
+              "enas_fanin: gx must be a contiguous [B, H, H, C] with a square map and C % 8 == 0");
+  TORCH_CHECK(B < (1 << 20) && H < (1 << 20) && C < (1 << 20), "enas_fanin: producer out of range");
+  TORCH_CHECK(!terms.empty() && (int64_t)terms.size() <= EF::kMaxTerms, "enas_fanin: 1 to ", EF::kMaxTerms,
+              " terms, got ", terms.size());
+  EF::Table tb{};
+  tb.n = (int)terms.size();
+  tb.B = (int)B, tb.H = (int)H, tb.C8 = (int)(C / 8);
+  for (int k = 0; k < tb.n; ++k) {
+    TORCH_CHECK(terms[k].size() == 3, "enas_fanin: terms are (g, off, relu)");
+    const Tensor g = terms[k][0].cast<Tensor>();
+    const int64_t off = terms[k][1].cast<int64_t>();
+    fanin_t(g, gx, "a term's gradient");
+    const int64_t m = g.size(1), Cg = g.size(3);
+    TORCH_CHECK(g.size(0) == B && g.size(2) == m && m >= H && m < (1 << 20) && Cg < (1 << 24),
+                "enas_fanin: a term's gradient is [B, m, m, Cg] with m >= H");
+    TORCH_CHECK(off >= 0 && off + C <= Cg, "enas_fanin: channels off .. off + C reach past the term's gradient");
+    TORCH_CHECK(Cg == 1 || g.stride(3) == 1, "enas_fanin: a term's channels must be adjacent");
+    // the pixel stride, from the first dimension that has one (a dimension of size 1 has no say)
+    const int64_t gs = m > 1 ? g.stride(2) : (B > 1 ? g.stride(0) : (Cg + 7) / 8 * 8);
+    TORCH_CHECK(gs >= Cg && gs % 8 == 0 && gs < (1ll << 31) && (m == 1 || g.stride(1) == m * gs) &&
+                    (B == 1 || g.stride(0) == m * m * gs),
+                "enas_fanin: a term's gradient must be dense up to a pixel stride >= Cg that is a multiple of 8");
+    const int sh = (int)(off % 8);
+    const int64_t last = (B * m * m - 1) * gs + (off / 8 + C / 8 + (sh ? 1 : 0)) * 8;  // one past the last element read
+    TORCH_CHECK((g.storage_offset() + last) * 2 <= (int64_t)g.storage().nbytes(), "enas_fanin: a term reaches past its storage");
+    if (sh) {
+      TORCH_CHECK(tb.sh == 0 || tb.sh == sh, "enas_fanin: the shifted terms of a launch share one off % 8");
+      tb.sh = sh;
+      tb.shift |= 1u << k;
+    }
+    if (terms[k][2].cast<bool>()) tb.relu |= 1u << k;
+    tb.k[k] = EF::Term{g.data_ptr(), (int)(gs / 8), (int)m, (int)((m - H) / 2), (int)(off / 8)};
+  }
+  if (tb.relu) {
+    TORCH_CHECK(x.has_value() && x->defined(), "enas_fanin: a ReLU term needs x");
+    fanin_t(*x, gx, "x");
+    TORCH_CHECK(x->is_contiguous() && x->sizes() == gx.sizes(), "enas_fanin: x must be contiguous and shaped like gx");
+    tb.x = x->data_ptr();
+  }
+  const char* why = EF::finish(tb, gx.data_ptr());
+  TORCH_CHECK(why == nullptr, "enas_fanin: ", why ? why : "");
+  TORCH_CHECK(EF::launch(tb, gx.data_ptr(), c10::hip::getCurrentHIPStream().stream()) == hipSuccess,
+              "enas_fanin launch failed");
+}
+
 }  // namespace
 
 void register_enas(py::module& m) {
+  m.def("enas_fanin", &enas_fanin,
+        "gradient of one layer output summed over all its readers: fp32 sum of up to 16 (g, off, relu) terms, the ReLU "
+        "terms behind the mask x > 0, one rounding to bf16");
   m.def("enas_adam_table", &adam_table, "validate + upload the segment table of the child's one-launch Adam");
   m.def("enas_adam", &adam,
         "one-launch Adam over every segment: zeroes the gradient buffers, sums the depthwise partials, re-emits "

@@ -35,6 +35,7 @@
 #include <climits>
 #include <cstdint>
 
+#include "enas_chunk.h"
 #include "enas_concat.h"
 
 namespace katib_hip {
@@ -44,11 +45,9 @@ namespace {
 
 constexpr int kChunks = 4;  // 16-byte chunks per thread, all in flight together
 
-// a bf16 widened to fp32 bits is <= 0: zero, or negative and no NaN (integer tests, so the answer
-// does not depend on the denormal mode)
-__device__ __forceinline__ bool le0(uint32_t f) {
-  return (int32_t)f <= 0 && (f & 0x7fffffffu) <= 0x7f800000u;
-}
+using enaschunk::funnel;  // enas_chunk.h: shared with the gradient fan-in
+using enaschunk::le0;
+using enaschunk::pin;
 
 // bf16 pair in a dword: the halves of g cleared where the half of x is <= 0
 __device__ __forceinline__ uint32_t keep2(uint32_t x, uint32_t g) {
@@ -62,9 +61,6 @@ __device__ __forceinline__ uint4 keep8(const uint4& x, const uint4& g) {
 __device__ __forceinline__ uint16_t keep1(uint16_t x, uint16_t g) {
   return le0((uint32_t)x << 16) ? (uint16_t)0 : g;
 }
-
-// the loaded chunk is live here: keeps the compiler from sinking a load below another chunk's store
-__device__ __forceinline__ void pin(uint4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z), "+v"(v.w)); }
 
 // index of the source whose channel range holds c (unused entries start at INT_MAX)
 __device__ __forceinline__ int find_src(const Table& tb, int c) {
@@ -162,18 +158,7 @@ __global__ void __launch_bounds__(256) concat_bwd_vec_k(const Table tb, const ui
 // at or behind o8 reads its chunk j from the last 8 - C of gout chunk off / 8 + j and the first C of
 // the next one.
 
-// eight bf16 out of the sixteen of (lo, hi), from element S on: a dword rotate for the even part of
-// S, v_alignbyte_b32 by two bytes for the odd half-word; S is a constant, so it is all register naming
-template <int S>
-__device__ __forceinline__ uint4 funnel(const uint4& lo, const uint4& hi) {
-  const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-  constexpr int d = S >> 1;
-  uint32_t r[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    r[j] = (S & 1) ? __builtin_amdgcn_alignbyte(w[(d + j + 1) & 7], w[d + j], 2u) : w[d + j];
-  return make_uint4(r[0], r[1], r[2], r[3]);
-}
+// (funnel<S>, the shift itself, is in enas_chunk.h)
 
 // Like concat_fwd_vec_k: no branch before the stores; the record fetches first (two a chunk, one
 // per half), then all 16-byte loads back to back, then the narrow source's C values of the chunk's

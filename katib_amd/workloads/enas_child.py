@@ -35,6 +35,10 @@ pointwise on MFMA, bias on the accumulator - and one launch for the pointwise ba
 depthwise result, which therefore never reaches HBM and is not kept for the backward; parameter names,
 ``state_dict()``, ``--optim`` and ``--head`` are untouched; the default ``split`` keeps the two layers' own
 kernels (ARCHITECTURE section 4, ``profiles/enas_sepconv.log``),
+with ``--gradsum hip`` the gradient of every layer output summed over all the layers that read it by one
+launch (``ops/enas_fanin.py``: the readers' concat backwards record their terms and write no gradient of
+their own; layer inputs then come from the concat kernels; the default ``autograd`` keeps one gradient per
+reader and the framework's adds),
 synthetic CIFAR-10-shaped data in HBM, and data parallelism over the trial's GPUs
 (``WORLD_SIZE`` ranks, RCCL all-reduce of the flat gradient) in place of
 ``tf.distribute.MirroredStrategy``.
@@ -69,6 +73,7 @@ from ..ops import conv as hconv
 from ..ops import pool as hpool
 from ..ops import dwconv as hdw
 from ..ops import enas_concat as hcat
+from ..ops import enas_fanin as hfan
 from ..ops import enas_head as hhead
 from ..ops import enas_sepconv as hsep
 from ..ops.augment import PLAIN, AugSpec, augment_gather, cifar_lut
@@ -182,10 +187,13 @@ def _concat(xs: List[torch.Tensor]):
 
 
 class ChildNet(nn.Module):
-    def __init__(self, arch, nn_config, sep="split"):
+    def __init__(self, arch, nn_config, sep="split", gradsum="autograd"):
         super().__init__()
         if sep not in ("split", "fused"):
             raise ValueError("sep must be 'split' or 'fused', got %r" % (sep,))
+        if gradsum not in ("autograd", "hip"):
+            raise ValueError("gradsum must be 'autograd' or 'hip', got %r" % (gradsum,))
+        self.gradsum = gradsum
         self.arch = arch
         self.num_layers = int(nn_config["num_layers"])
         c, h, w = _chw(nn_config["input_sizes"])
@@ -208,8 +216,36 @@ class ChildNet(nn.Module):
         self.drop = nn.Dropout(0.4)
         self.fc = nn.Linear(chans[-1], int(nn_config["output_sizes"][-1]))
 
+    def _features_fanin(self, x):
+        """``features`` with ``gradsum='hip'`` on a GPU: every layer input the concat kernels serve comes
+        from them, and every layer output with such a reader goes through ``share``, so its gradient is
+        summed over all its readers by one fan-in launch (``ops/enas_fanin.py``). A 67-channel output behind
+        a depthwise layer (``C % 8 != 0``) is not shared and keeps the autograd sum."""
+        layers, fans = [x], [None]
+        for l, (op, ins) in enumerate(zip(self.ops, self.inputs), 1):
+            srcs = [layers[i] for i in ins]
+            pool = op.kind == "reduction"
+            if (PAD8_INPUT and op.kind == "convolution" and len(srcs) > 1
+                    and sum(s.shape[1] for s in srcs) % 8 and hcat.supported(srcs, pad8=True)):
+                y = op(hcat.relu_pad_concat(srcs, relu=True, pad8=True, fans=[fans[i] for i in ins]), relu_done=True)
+            elif not (pool and len(srcs) == 1) and hcat.supported(srcs):
+                y = op(hcat.relu_pad_concat(srcs, relu=not pool, fans=[fans[i] for i in ins]), relu_done=True)
+            else:
+                y = op(_concat(srcs))
+            # a reader through the concat kernels: any later layer but a `reduction` that reads this one alone
+            read = any(l in later and not (o.kind == "reduction" and len(later) == 1)
+                       for o, later in zip(self.ops[l:], self.inputs[l:]))
+            fan = None
+            if read and y.requires_grad and hfan.servable(y):
+                y, fan = hfan.share(y)
+            layers.append(y)
+            fans.append(fan)
+        return layers[-1]
+
     def features(self, x):
         """The last layer's activation, the input of the head."""
+        if self.gradsum == "hip" and x.is_cuda:
+            return self._features_fanin(x)
         layers = [x]
         for op, ins in zip(self.ops, self.inputs):
             srcs = [layers[i] for i in ins]
@@ -269,6 +305,10 @@ def parse_args(argv):
     p.add_argument("--sep", type=str, default="split", choices=["split", "fused"],
                    help="separable_convolution: split = depthwise and pointwise kernels with the depthwise result in "
                         "HBM, fused = one HIP launch per direction where the fused kernels serve the layer")
+    p.add_argument("--gradsum", type=str, default="autograd", choices=["autograd", "hip"],
+                   help="gradient of a layer read by several later layers: autograd = one gradient per reader, added "
+                        "by the framework, hip = one HIP launch per layer that sums over all its readers (and every "
+                        "layer input the concat kernels serve built by them)")
     return p.parse_args(argv)
 
 
@@ -280,7 +320,7 @@ class ChildTrainer:
     ``index_select``."""
 
     def __init__(self, arch, nn_config, num_train=50000, num_valid=10000, batch_size=128, capture=True, seed=0,
-                 comm=None, data_dir="", augment=False, head="module", optim="module", sep="split"):
+                 comm=None, data_dir="", augment=False, head="module", optim="module", sep="split", gradsum="autograd"):
         from ..parallel.comm import Comm
 
         dev = device()
@@ -292,6 +332,8 @@ class ChildTrainer:
         if optim == "hip" and not (cuda and self.comm.world_size == 1):
             raise ValueError("--optim hip needs a GPU and world_size == 1 (the gradient all-reduce does not reach "
                              "the optimizer's buffers); got device %s, world_size %d" % (dev.type, self.comm.world_size))
+        if gradsum == "hip" and not cuda:
+            raise ValueError("--gradsum hip needs a GPU; got device %s" % dev.type)
         self.optim = optim
         self.dev, self.cuda = dev, cuda
         mf = torch.channels_last if cuda else torch.contiguous_format
@@ -327,7 +369,7 @@ class ChildTrainer:
             spec = PLAIN
         if gather:
             self.xb = torch.empty(batch_size, h, w, c, dtype=torch.bfloat16, device=dev)
-        self.model = model = ChildNet(arch, nn_config, sep).to(dev).to(memory_format=mf)
+        self.model = model = ChildNet(arch, nn_config, sep, gradsum).to(dev).to(memory_format=mf)
         comm = self.comm
         if comm.world_size > 1:  # every rank starts from rank 0's weights
             flat0 = torch.nn.utils.parameters_to_vector(model.parameters()).detach()
@@ -445,7 +487,8 @@ def main(argv=None):
     print(">>> arch received by trial\n%s" % arch, flush=True)
     augment = bool(args.data_dir) if args.augment == "auto" else args.augment == "1"
     tr = ChildTrainer(arch, nn_config, args.num_train, args.num_valid, args.batch_size, bool(args.capture), args.seed,
-                      data_dir=args.data_dir, augment=augment, head=args.head, optim=args.optim, sep=args.sep)
+                      data_dir=args.data_dir, augment=augment, head=args.head, optim=args.optim, sep=args.sep,
+                      gradsum=args.gradsum)
     comm, dev, bs, steps = tr.comm, tr.dev, tr.bs, tr.steps
     gen = torch.Generator(device=dev).manual_seed(args.seed + comm.rank)
     timer = Timer()
